@@ -9,7 +9,14 @@ image (spp camera samples per pixel, each 1 primary + 1 sun-shadow + 1 IBL-occlu
 traversal, ReSTIR spatial+temporal reuse, accumulation, Welford).  Inputs (DEM tables,
 state) are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed frames, times K frames and prints one JSON line
+(`ms_per_step`: milliseconds per timed frame).  --dump-outputs DIR then writes the image of
+the last timed frame (RGBA, albedo, normal, depth, hit mask) as finite float32 .npy files.
+--full adds what the headline does not need: the golden scene's SSIM, further timed windows
+and the kernel-timing window, the CPU baseline and the rooflines, the terrain-filling
+camera, a real DEM when one is supplied, and BASELINE.json's other configurations.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): the image is split into N
 load-balanced row strips (measured before the timed region, forge3d_amd/distributed.py).
@@ -77,15 +84,25 @@ def parse_args():
     ap.add_argument("--spp", type=int, default=8)
     ap.add_argument("--dem", type=int, default=2048)
     ap.add_argument("--variant", type=int, default=int(os.environ.get("F3D_KERNEL_VARIANT", "0")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the golden scene's SSIM, further timed windows and the "
+                         "kernel-timing window, the CPU baseline and the rooflines, the terrain-filling camera, a real DEM, BASELINE.json's "
+                         "other configurations.  Without it the run sets up, warms up, times --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the image the timed path produced in its last frame as DIR/<name>.npy "
+                         "(float32, finite: rgba, albedo, normal, depth with 0 where the ray hit nothing, hit = 1 or 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and with it the rooflines)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--extra-windows", type=int, default=4, help="further timed windows of --steps frames (spread report)")
+    ap.add_argument("--extra-windows", type=int, default=4, help="--full: further timed windows of --steps frames (spread report)")
     ap.add_argument("--no-recut", action="store_true", help="N > 1: keep the first cut of the strips whatever the warm-up frames cost each rank")
-    ap.add_argument("--no-terrain-filling", action="store_true", help="skip the second, terrain-filling camera")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short timed windows of BASELINE.json's other configurations")
-    ap.add_argument("--dem-path", default=None, help="a real DEM (GeoTIFF / .npy) for an ADDITIONAL labelled run of the headline configuration; "
+    ap.add_argument("--no-terrain-filling", action="store_true", help="--full: skip the second, terrain-filling camera")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the short timed windows of BASELINE.json's other configurations")
+    ap.add_argument("--dem-path", default=None, help="--full: a real DEM (GeoTIFF / .npy) for an ADDITIONAL labelled run of the headline configuration; "
                                                      "default: $FORGE3D_REPO_ROOT/assets/tif/dem_rainier.tif when that exists (BASELINE.md section 3)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def kernel_source_hash() -> str:
@@ -353,6 +370,34 @@ def cpu_baseline(dem, cam, kw, args, world=1):
     }, counts
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much
+DUMP_SEED = 20261016
+
+
+def dump_outputs(directory, image) -> None:
+    """--dump-outputs: the arrays a caller of the renderer receives (resolve: RGBA8, albedo, normal, depth) as float32 .npy
+    files, every value finite.  The renderer marks a pixel whose camera ray hits nothing (sky) with a NaN depth; the dump
+    writes depth 0 there and says which pixels hit in `hit` (1.0 terrain, 0.0 sky) -- a hit's depth is a positive distance.
+    When the whole image does not fit in DUMP_BYTES, every array keeps the same fixed, seeded sample of pixels in raster
+    order, shape (pixels, channels); otherwise the arrays keep their image shape."""
+    arrays = {key: np.asarray(image[key]).astype(np.float32) for key in ("rgba", "albedo", "normal", "depth")}
+    hit = ~np.isnan(arrays["depth"])
+    arrays["depth"] = np.where(hit, arrays["depth"], np.float32(0.0))
+    arrays["hit"] = hit.astype(np.float32)
+    bad = [key for key, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:  # anything else that is not finite is a defect of the render, not a value to write
+        raise ValueError(f"--dump-outputs: non-finite values in {', '.join(bad)} of the last timed frame")
+    h, w = arrays["depth"].shape[:2]
+    pixel_bytes = sum(a[0, 0].nbytes for a in arrays.values())
+    if h * w * pixel_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, DUMP_BYTES // pixel_bytes, replace=False))
+        arrays = {key: a.reshape(h * w, -1)[keep] for key, a in arrays.items()}
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(out / f"{key}.npy", a)
+
+
 def pmc_kernel_ms(issue: dict):
     """Average duration of the profiled launches behind an `issue` block (tools/gpu_profile.sh stores it), or None."""
     v = issue.get("kernel_ms_profiled")
@@ -420,8 +465,9 @@ def main():
     dem, cam, kw = datasets.rainier_proxy_scene(args.dem)
     kw = dict(kw, spp=args.spp, variance_threshold=1e30)
 
-    windows = 1 + max(0, args.extra_windows)
-    total_frames = args.warmup + args.steps * max(windows, 2)  # (one window more when the kernel-timing window is an extra one)
+    # a plain run times one window and accumulates nothing after it; --full adds the further windows and the kernel-timing one
+    windows = 1 + max(0, args.extra_windows) if args.full else 1
+    total_frames = args.warmup + args.steps * (max(windows, 2) if args.full else 1)  # (one window more when the kernel-timing window is an extra one)
     kw = dict(kw, max_frames=max(total_frames, 2), min_frames=max(total_frames, 2))
     if True:  # (every rank) a throw-away session of another DEM first: module load and allocator start-up are not set-up of THIS render
         from forge3d_amd.session import TerrainSession
@@ -434,7 +480,7 @@ def main():
         torch.zeros(4, dtype=torch.int32, device=f"cuda:{local_rank}")  # (torch's own allocator and stream start up with its first device tensor: 15-20 ms on some boxes)
         torch.cuda.synchronize()
     golden_report = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # the reference's golden scene, rendered and scored for the line's "SSIM vs golden" -- in front of the set-up and the timed
         # windows rather than behind them: it is 256 frames of device work the bench does anyway, and a device that has just
         # done it runs the first timed window at the clocks of the later ones (it used to be 1.5 % slower than windows 2-5)
@@ -509,12 +555,14 @@ def main():
     halo_wait_ms = r._gather_floats(sum(halo["wait_ms"]) / args.steps) if (world > 1 and halo) else None
     halo_longest_ms = r._gather_floats(halo["longest_wait_ms"]) if (world > 1 and halo) else None
     elapsed = r.max_over_ranks(elapsed)
-    # further windows of the same K frames (the accumulation simply continues): the spread of the measurement.  The
+    # what the timed path computed in its last frame, as its caller receives it (rank 0; every rank takes part in the gather)
+    last_image = r.gather_image(args.warmup + args.steps) if (args.dump_outputs or not args.full) else None
+    # --full: further windows of the same K frames (the accumulation simply continues): the spread of the measurement.  The
     # frame kernel is timed (two hip events around every launch) in the LAST of them, or -- with --extra-windows 0 --
     # in a window of its own after the timed region: the headline window runs without the events.
     window_ms = [elapsed / args.steps * 1e3]
     kernel_ms, launches = 0.0, 0
-    for wi in range(1, windows + (1 if windows == 1 else 0)):
+    for wi in range(1, windows + (1 if windows == 1 else 0)) if args.full else ():
         timed_kernels = wi == max(1, windows - 1)
         r.barrier()
         torch.cuda.synchronize()
@@ -531,7 +579,7 @@ def main():
         if wi < windows:
             window_ms.append(dt)
     # final composition (untimed, but exercised): gather strips to rank 0
-    image = r.gather_image(total_frames)
+    image = r.gather_image(total_frames) if args.full else last_image
     halo_bytes = 0 if world == 1 else HALO_ROWS * args.width * 16 * ((1 if rank > 0 else 0) + (1 if rank < world - 1 else 0))
     warnings = []
     if world > 1:
@@ -603,7 +651,7 @@ def main():
             },
         }
         counts = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 baseline, counts = cpu_baseline(dem, cam, kw, args, world)
                 if baseline is not None:  # reported at N = 1 only
@@ -678,7 +726,7 @@ def main():
     r.close()
     if rank == 0 and golden_report is not None:
         result.update(golden_report)
-    if rank == 0 and world == 1 and not args.no_terrain_filling:
+    if args.full and rank == 0 and world == 1 and not args.no_terrain_filling:
         # the same DEM from inside the footprint: (nearly) every sample is shaded -- a harder number than the headline
         cam2 = terrain_filling_camera(dem, kw)
         frames2 = 4 + 16
@@ -699,7 +747,7 @@ def main():
             "shaded_msamples_per_s": rate2 * hit2, "grays_per_s": rate2 * 1e6 * (1.0 + 2.0 * hit2) / 1e9,
             "camera": {k: [float(x) for x in v] if isinstance(v, tuple) else v for k, v in cam2.items()},
         }
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # "if a real dem_rainier.tif is supplied via FORGE3D_REPO_ROOT, S2 is run on it as well and
         # labelled" (reference python/forge3d/datasets.py:53-61, :312 fetch_dem('rainier')).  The headline stays the proxy.
         real_path = args.dem_path
@@ -728,7 +776,7 @@ def main():
                                              "image_mean_rgb": [float(x) for x in img3["rgba"][..., :3].mean((0, 1))]}
             except Exception as exc:  # noqa: BLE001 -- an unreadable file must not cost the headline
                 result["config_real_dem"] = {"error": str(exc)[:300], "data": f"real DEM {real_path}"}
-    if rank == 0 and world == 1 and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_configs:
         result["configs"] = other_configs(dem, cam, kw, args, local_rank)
         # roofline rows of these configurations' dominant kernels (and of the multi-GPU strip form) from the rocprofv3 passes
         # committed under profiles/ (tools/gpu_profile_config.sh -> tools/config_rooflines.py): quoted only for THESE kernel sources
@@ -751,6 +799,8 @@ def main():
                 break
         except Exception:  # noqa: BLE001 -- a report, never a reason to lose the line
             pass
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_image)
     if rank == 0:
         print(json.dumps(result))
 

@@ -1,11 +1,12 @@
 """Host logic of bench.py that only an N > 1 run exercises on hardware: the one re-cut of the strips after the warm-up frames
- and the identity fields.  No GPU."""
+ and the identity fields; the options of a plain run and what --dump-outputs writes.  No GPU."""
 from __future__ import annotations
 
 import sys
 from pathlib import Path
 
 import numpy as np
+import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -75,3 +76,61 @@ def test_device_identity_reports_whatever_the_torch_build_exposes():
 
     ident = bench.device_identity(Torch(), 3)
     assert ident == {"index": 3, "name": "AMD Instinct MI355X", "uuid": "abc", "pci_bus_id": "5"}
+
+
+def _image(h, w, seed=0):
+    rng = np.random.default_rng(seed)
+    depth = rng.uniform(1.0, 9.0, (h, w)).astype(np.float32)
+    depth[0, :3] = np.nan  # sky: the renderer's miss marker
+    return {"rgba": rng.integers(0, 256, (h, w, 4), dtype=np.uint8), "albedo": rng.random((h, w, 3), np.float32),
+            "normal": rng.random((h, w, 3), np.float32), "depth": depth, "any_valid_reservoir": True}
+
+
+def test_dump_outputs_writes_the_image_as_finite_float32(tmp_path):
+    img = _image(6, 10)
+    bench.dump_outputs(tmp_path / "out", img)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["albedo.npy", "depth.npy", "hit.npy", "normal.npy", "rgba.npy"]
+    for key in ("rgba", "albedo", "normal"):
+        got = np.load(tmp_path / "out" / f"{key}.npy")
+        assert got.dtype == np.float32 and got.shape == img[key].shape
+        assert np.array_equal(got, img[key].astype(np.float32))
+    depth, hit = np.load(tmp_path / "out" / "depth.npy"), np.load(tmp_path / "out" / "hit.npy")
+    assert depth.dtype == hit.dtype == np.float32 and depth.shape == hit.shape == (6, 10)
+    assert np.isfinite(depth).all() and set(np.unique(hit)) == {0.0, 1.0}
+    sky = np.isnan(img["depth"])
+    assert np.array_equal(hit == 0.0, sky) and (depth[sky] == 0.0).all() and np.array_equal(depth[~sky], img["depth"][~sky])
+
+
+def test_dump_outputs_refuses_a_non_finite_value_it_cannot_explain(tmp_path):
+    img = _image(4, 4)
+    img["albedo"][1, 2, 0] = np.inf
+    with pytest.raises(ValueError, match="albedo"):
+        bench.dump_outputs(tmp_path / "out", img)
+    assert not (tmp_path / "out").exists()
+
+
+def test_dump_outputs_samples_the_same_pixels_when_the_image_is_too_large(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_BYTES", 48 * 100)  # 100 pixels of 12 float32 channels
+    img = _image(20, 30, seed=1)
+    bench.dump_outputs(tmp_path / "a", img)
+    bench.dump_outputs(tmp_path / "b", _image(20, 30, seed=1))
+    total = 0
+    for key, chans in (("rgba", 4), ("albedo", 3), ("normal", 3), ("depth", 1), ("hit", 1)):
+        a, b = np.load(tmp_path / "a" / f"{key}.npy"), np.load(tmp_path / "b" / f"{key}.npy")
+        assert a.dtype == np.float32 and a.shape == (100, chans) and np.isfinite(a).all() and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_BYTES
+    # the rows are pixels of the image, in raster order, the same pixels for every array
+    first_albedo = img["albedo"][..., 0].reshape(-1)
+    idx = [int(np.flatnonzero(first_albedo == v)[0]) for v in np.load(tmp_path / "a" / "albedo.npy")[:, 0]]
+    assert idx == sorted(idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "rgba.npy"), img["rgba"].reshape(-1, 4)[idx].astype(np.float32))
+
+
+def test_a_plain_run_is_the_default_and_steps_are_what_was_asked(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    args = bench.parse_args()
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == "d" and args.steps == 32

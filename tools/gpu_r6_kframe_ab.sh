@@ -6,7 +6,7 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/keep; LOG=gpurun_out/keep/r06_kframe_ab.log; : > $LOG
 run() {  # name lib env...
   name=$1; lib=$2; shift 2
-  env "$@" F3D_HIP_LIBRARY=$lib python bench.py --steps 16 --warmup 4 --no-cpu-baseline --extra-windows 2 --no-terrain-filling --no-configs 2>&1 | tail -1 | python -c "
+  env "$@" F3D_HIP_LIBRARY=$lib python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline --extra-windows 2 --no-terrain-filling --no-configs 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('%-34s %.1f Msamples/s  windows %s  setup %.2f ms  rgb %s' % ('$name', d['value'], d.get('windows_ms_per_step'), d['config']['setup_ms_once_per_render'], d['config']['image_mean_rgb']))" | tee -a $LOG
 }

@@ -18,7 +18,7 @@ unset OMP_NUM_THREADS
 bash tools/gpu_profile.sh 0 $TAG > gpurun_out/profile_$TAG.log 2>&1; tail -1 gpurun_out/profile_$TAG.log | cut -c1-400
 cp gpurun_out/prof_$TAG/pmc_traffic.json gpurun_out/prof_$TAG/summary.txt $K/ 2>/dev/null
 cp gpurun_out/prof_$TAG/pmc_traffic.json profiles/${TAG}_pmc_traffic.json
-timeout 600 python bench.py > $K/bench_$TAG.json 2> $K/bench_$TAG.err; cut -c1-300 $K/bench_$TAG.json
+timeout 600 python bench.py --full > $K/bench_$TAG.json 2> $K/bench_$TAG.err; cut -c1-300 $K/bench_$TAG.json
 rm -rf gpurun_out/prof_$TAG/*/
 if [ $MODE = full ]; then
   for n in 2 4; do
