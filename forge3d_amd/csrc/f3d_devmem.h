@@ -113,9 +113,10 @@ struct SmokeContext {
     hipEvent_t fields_read = nullptr;
     unsigned long long id = 0;  // 0: the thread's default context (scratch named by stream, as in ABI 5); else "#id"
     bool async_ok = false;      // may a call whose results stay on the device return with its launches enqueued?
-    // the marcher's deferred self-shadow list of the last render: capacity, and where its fill count lives (read on request)
+    // the capacity of the marcher's deferred self-shadow list in the last render (0: none).  Its fill count lives in the
+    // workspace buffer "smoke.render.shadow.cursor" and is looked up by name when asked for (workspace_find): not a pointer
+    // kept here, since f3d_device_pool_trim frees the workspace of live contexts too.
     uint32_t shadow_capacity = 0;
-    const uint32_t *shadow_cursor = nullptr;
 };
 inline SmokeContext &thread_default_smoke_context() {
     static thread_local SmokeContext context;
@@ -161,6 +162,11 @@ inline hipError_t workspace(void **out, const char *tag, size_t bytes) {
     }
     *out = w.p;
     return hipSuccess;
+}
+// (call with workspace_lock() held) the buffer of `tag` + `suffix` on `device`; nullptr: none (never allocated, or trimmed)
+inline void *workspace_find(int device, const char *tag, const std::string &suffix) {
+    const auto it = workspace_map().find({device, std::string(tag) + suffix});
+    return it == workspace_map().end() ? nullptr : it->second.p;
 }
 // Bytes of scratch held for one name space ("#id" / "@stream"), and their release (a sequence handle that goes away).
 inline size_t workspace_bytes(const std::string &suffix) {

@@ -396,14 +396,18 @@ std::shared_ptr<CachedMesh> acquire_mesh(int device, const float *vertices, uint
                                          uint32_t builder, hipStream_t stream) {
     const uint64_t key_v = hash_bytes(vertices, (size_t)vertex_count * 3u * sizeof(float), 0x6D657368ull);
     const uint64_t key_i = hash_bytes(indices, (size_t)index_count * sizeof(uint32_t), 0x696E6478ull);
-    {
-        std::lock_guard<std::mutex> lock(g_scene_mutex);
+    auto cached = [&]() -> std::shared_ptr<CachedMesh> {  // (call with g_scene_mutex held)
         for (auto &e : g_mesh_cache)
             if (e->device == device && e->key_v == key_v && e->key_i == key_i && e->vertex_count == vertex_count && e->index_count == index_count &&
                 e->builder == builder) {
                 e->stamp = ++g_scene_stamp;
                 return e;
             }
+        return nullptr;
+    };
+    {
+        std::lock_guard<std::mutex> lock(g_scene_mutex);
+        if (auto hit = cached()) return hit;
     }
     auto e = std::make_shared<CachedMesh>();
     e->device = device;
@@ -426,14 +430,14 @@ std::shared_ptr<CachedMesh> acquire_mesh(int device, const float *vertices, uint
     if (builder == 2u) {
         LbvhResult lb;
         hip_check(build_mesh_lbvh(dv, vertex_count, di, index_count, stream, &lb), "GPU LBVH build");
-        hip_check(hipStreamSynchronize(stream), "GPU LBVH build");  // other sessions may walk it from their streams
-        if (lb.nodes) {
+        if (lb.nodes) {  // (owned by the entry before anything can throw: a failed wait below frees them with it)
             e->mem.adopt(lb.nodes, lb.node_bytes);
             e->mem.adopt(lb.tris, lb.tri_bytes);
             M.bvh_nodes = lb.nodes;
             M.bvh_tris = lb.tris;
             M.bvh_node_count = lb.node_count;
         }
+        hip_check(hipStreamSynchronize(stream), "GPU LBVH build");  // other sessions may walk it from their streams
     } else {
         const MeshBvh bvh = build_mesh_bvh(vertices, vertex_count, indices, index_count);
         if (!bvh.nodes.empty()) {
@@ -458,6 +462,9 @@ std::shared_ptr<CachedMesh> acquire_mesh(int device, const float *vertices, uint
         }
     }
     std::lock_guard<std::mutex> lock(g_scene_mutex);
+    // another session may have built the same mesh while this one did (both missed above): one entry, theirs; the copy built
+    // here goes when `e` does, after the lock (declared before it)
+    if (auto hit = cached()) return hit;
     e->stamp = ++g_scene_stamp;
     if (g_scene_limit > 0) {
         g_mesh_cache.push_back(e);

@@ -404,6 +404,7 @@ constexpr uint32_t kChunkRows = 16u, kChunkSlots = kChunkRows * 64u, kNoChunk = 
 // (1080p, 96 x 64 x 128 plume, frame 160): 3 373 chunks used of the 8 100 this gives (f3d_smoke_seq_stats; 432 MB).  A tile whose
 // steps do not fit is walked in the one-kernel form by k_smoke_shade: slower, same pixels.
 constexpr size_t kListStepsPerPixel = 4u, kListCapMb = 1024u;
+constexpr const char *kShadowCursorTag = "smoke.render.shadow.cursor";  // the list's fill count (read by f3d_smoke_seq_stats)
 struct Deferred {
     float4 *where;       // per slot: the step's position, and its extinction sigma_t
     float4 *fields;      // per slot: density, soot, age, temperature as interpolated there
@@ -865,11 +866,10 @@ extern "C" int f3d_smoke_render(const f3d_smoke_volume *vol, const f3d_smoke_vie
             D.chunk_of = (uint32_t *)named("smoke.render.shadow.chunk_of", (size_t)tiles * D.chunks_per_tile * sizeof(uint32_t));
             D.owner = (uint2 *)named("smoke.render.shadow.owner", (size_t)D.capacity * sizeof(uint2));
             D.count = (uint32_t *)named("smoke.render.shadow.count", px * sizeof(uint32_t));
-            D.cursor = (uint32_t *)named("smoke.render.shadow.cursor", sizeof(uint32_t));
+            D.cursor = (uint32_t *)named(kShadowCursorTag, sizeof(uint32_t));
             if (out_of_memory) deferred = false;  // the one-kernel form needs no list
         }
         current_smoke_context()->shadow_capacity = deferred ? D.capacity : 0u;
-        current_smoke_context()->shadow_cursor = deferred ? D.cursor : nullptr;
         if (deferred) {
             hip_ok(hipMemsetAsync(D.cursor, 0, sizeof(uint32_t), call_stream()), "smoke shadow list");
             const size_t lds = ((size_t)D.chunks_per_tile + 1u) * sizeof(uint32_t);
@@ -1033,14 +1033,19 @@ extern "C" int f3d_smoke_seq_stats(f3d_smoke_seq *q, f3d_smoke_seq_stats_t *out,
     char suffix[40];
     snprintf(suffix, sizeof(suffix), "#%llu", q->ctx.id);
     out->scratch_bytes = workspace_bytes(suffix);
-    out->shadow_list_chunks = q->ctx.shadow_capacity;
+    out->shadow_list_chunks = 0u;
     out->shadow_list_chunks_used = 0u;
     out->shadow_list_slots_per_chunk = kChunkSlots;
-    if (q->ctx.shadow_cursor) {
-        if (hipStreamSynchronize(q->march) != hipSuccess) return seq_fail(err, errlen, F3D_STATUS_DEVICE, "the marcher's stream failed");
-        uint32_t used = 0u;
-        if (hipMemcpy(&used, q->ctx.shadow_cursor, sizeof(used), hipMemcpyDeviceToHost) != hipSuccess) return seq_fail(err, errlen, F3D_STATUS_DEVICE, "could not read the list's fill count");
-        out->shadow_list_chunks_used = used;  // (may exceed the capacity: that many were asked for; the excess was walked in the one-kernel form)
+    if (q->ctx.shadow_capacity != 0u) {
+        // the fill count by name, under the lock: f3d_device_pool_trim may have freed the list since the render (then: no list)
+        std::lock_guard<std::mutex> lock(workspace_lock());
+        if (const void *cursor = workspace_find(q->device, kShadowCursorTag, suffix)) {
+            if (hipStreamSynchronize(q->march) != hipSuccess) return seq_fail(err, errlen, F3D_STATUS_DEVICE, "the marcher's stream failed");
+            uint32_t used = 0u;
+            if (hipMemcpy(&used, cursor, sizeof(used), hipMemcpyDeviceToHost) != hipSuccess) return seq_fail(err, errlen, F3D_STATUS_DEVICE, "could not read the list's fill count");
+            out->shadow_list_chunks = q->ctx.shadow_capacity;
+            out->shadow_list_chunks_used = used;  // (may exceed the capacity: that many were asked for; the excess was walked in the one-kernel form)
+        }
     }
     return F3D_STATUS_OK;
 }

@@ -509,6 +509,9 @@ int f3d_smoke_seq_step(f3d_smoke_seq *seq, f3d_smoke_state *state, const f3d_smo
 int f3d_smoke_seq_render(f3d_smoke_seq *seq, const f3d_smoke_volume *volume, const f3d_smoke_view *view, const f3d_smoke_settings *settings,
                          uint8_t *rgba, double *kernel_seconds, char *err, size_t errlen);
 int f3d_smoke_seq_composite(f3d_smoke_seq *seq, const f3d_composite_desc *desc, uint8_t *out_rgba, double *kernel_seconds, char *err, size_t errlen);
+/* What the sequence holds and the fill of its last render's self-shadow list (waits for that render).  After
+ * f3d_device_pool_trim, which frees the scratch of live sequences too, it reports scratch_bytes = 0 until the next step
+ * or render, and no list (shadow_list_chunks = shadow_list_chunks_used = 0) until the next render. */
 int f3d_smoke_seq_stats(f3d_smoke_seq *seq, f3d_smoke_seq_stats_t *out, char *err, size_t errlen);
 
 /* ---- AETHER acceptance reference: stochastic spectral transport (no LUT, black environment) ----
