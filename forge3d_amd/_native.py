@@ -19,6 +19,7 @@ LIB_PATH = _PKG / "libf3dhip.so"
 
 STATUS_OK, STATUS_VALUE, STATUS_RENDER, STATUS_UPLOAD, STATUS_DEVICE = 0, 1, 2, 3, 4
 ABI_VERSION = 6  # F3D_ABI_VERSION of include/f3d_terrain_pt.h this mirror was written against
+FRAMES_IN_FLIGHT_AUTO = 0xFFFFFFFF  # f3d_session_opts.frames_in_flight: what f3d_terrain_ref_render uses
 
 _EARTH = {"flat": 0, "sphere": 1, "ellipsoid": 2, "wgs84": 2}
 _REFRACTION = {"none": 0, "bennett": 1, "saemundsson": 2, "effective_radius": 3}
@@ -99,6 +100,20 @@ class SessionOpts(C.Structure):
     ]
 
 
+class RearmDesc(C.Structure):
+    """f3d_session_rearm_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("sun_azimuth_deg", C.c_float), ("sun_elevation_deg", C.c_float), ("sun_intensity", C.c_float),
+        ("sun_color", C.c_float * 3),
+        ("exposure", C.c_float), ("env_intensity", C.c_float),
+        ("seed", C.c_uint32), ("max_frames", C.c_uint32), ("min_frames", C.c_uint32),
+        ("variance_threshold", C.c_float),
+        ("observer_latitude_deg", C.c_double), ("observer_longitude_deg", C.c_double),
+        ("pressure_mbar", C.c_double), ("temperature_c", C.c_double),
+    ]
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -130,6 +145,10 @@ ABI = [
     ("f3d_aether_reference_render", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     ("f3d_smoke_composite", C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), C.c_char_p, C.c_size_t]),
     ("f3d_session_fingerprint", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    # re-arm of a live session (no ABI version bump: detected by the symbol)
+    ("f3d_session_rearm", C.c_int, [C.c_void_p, _P(RearmDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_render", C.c_int, [C.c_void_p, _P(Out), C.c_char_p, C.c_size_t]),
+    ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
     ("f3d_session_halo", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p), _P(C.c_uint64)]),
     ("f3d_session_resolve", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -485,6 +504,11 @@ def hybrid_render_terrain_reference(heightmap, width, height, cam, spacing=(1.0,
     del keep
     if rc != 0:
         raise_status(rc, err.value.decode("utf-8", "replace"))
+    return result_dict(rgba, alb, nrm, dep, o, sun_azimuth_deg, sun_elevation_deg)
+
+
+def result_dict(rgba, alb, nrm, dep, o, sun_azimuth_deg, sun_elevation_deg):
+    """The result dict of a render (f3d_terrain_ref_render, f3d_session_render) from its arrays and f3d_terrain_ref_out."""
     return {
         "rgba": rgba, "albedo": alb, "normal": nrm, "depth": dep,
         "frames": int(o.frames), "variance": float(o.variance), "converged": bool(o.converged),

@@ -115,6 +115,10 @@ struct f3d_session {
     int variant = 0;
     AetherDev aether{};  // enabled = 0 without desc.atmosphere
     bool require_valid_reservoirs = false;
+    // the descriptor the session renders, its pointers cleared (they are only read during the create): what a re-arm
+    // (f3d_session_rearm) starts from and what f3d_session_render's loop reads its frame budget from
+    f3d_terrain_ref_desc desc{};
+    bool rendered = false;  // f3d_session_render has run since the create or the last re-arm (its state is spent)
     uint64_t budget = 0;
     // band pipelining (f3d_session_opts.bands): horizontal bands of the strip, their streams and events
     struct Band {
@@ -163,6 +167,18 @@ struct f3d_session {
 namespace {
 
 void plan_bands(f3d_session &s, uint32_t want, uint32_t want_streams);
+
+// The sun-dependent scalars of the AETHER record: set by upload_aether, and again by a re-arm (the LUTs stay).
+void aether_sun_terms(AetherDev &A, const f3d_terrain_ref_desc &d) {
+    A.sun_intensity = aether_clamp_scale(f_clamp(d.sun_intensity, 0.0f, 65504.0f));
+    A.exposure = aether_clamp_scale(f_clamp(d.exposure, 0.0f, 65504.0f));
+}
+
+// same_sun: the two sun directions the frame head chooses between (wi, normalize(wi)) are the same bits
+uint32_t same_sun_of(const FrameParams &P) {
+    return f_bits(P.light.wi.x) == f_bits(P.light.wi_reuse.x) && f_bits(P.light.wi.y) == f_bits(P.light.wi_reuse.y) &&
+                   f_bits(P.light.wi.z) == f_bits(P.light.wi_reuse.z) ? 1u : 0u;
+}
 
 // AETHER LUT payload -> device tables (reference AetherPostPass::new, aether_post.rs:42-100: config.validate,
 // validate_luts, three RGBA16F texture uploads).  The tables are decoded to float4 once here.
@@ -234,8 +250,7 @@ void upload_aether(f3d_session &s, const f3d_aether_luts &L, const f3d_terrain_r
     A.max_aerial_distance = L.max_aerial_distance_m;
     A.ozone_du = L.ozone_du;
     A.turbidity = L.turbidity;
-    A.sun_intensity = aether_clamp_scale(f_clamp(d.sun_intensity, 0.0f, 65504.0f));
-    A.exposure = aether_clamp_scale(f_clamp(d.exposure, 0.0f, 65504.0f));
+    aether_sun_terms(A, d);
     A.enabled = 1u;
 }
 
@@ -284,6 +299,12 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
 
     FrameParams &P = s.params;
     s.require_valid_reservoirs = fill_uniforms(d, P);  // curvature, camera, lighting
+    s.desc = d;
+    s.desc.heights = nullptr;
+    s.desc.env_map = nullptr;
+    s.desc.mesh_vertices = nullptr;
+    s.desc.mesh_indices = nullptr;
+    s.desc.atmosphere = nullptr;
     clock.lap(kSetupValidate);
 
     // DEM upload + GPU table build (reference: CPU build + per-level write_texture), or the cached tables of this DEM
@@ -440,9 +461,7 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
             const uint64_t waves = ((uint64_t)px * P.sample_lanes + 63u) / 64u;
             want = waves < 2u * 6144u ? 16u : 0u;
         }
-        const bool same_sun = f_bits(P.light.wi.x) == f_bits(P.light.wi_reuse.x) && f_bits(P.light.wi.y) == f_bits(P.light.wi_reuse.y) &&
-                              f_bits(P.light.wi.z) == f_bits(P.light.wi_reuse.z);
-        P.same_sun = same_sun ? 1u : 0u;
+        P.same_sun = same_sun_of(P);
         // Wavefront trace (terrain-only scenes: the mesh walk stays in the fused kernels): F3D_WAVEFRONT=1 asks for it,
         // =0 forbids it; it needs frames in flight (F3D_WF_FRAMES, default 2) and 84 instead of 32 bytes per sample in flight.
         const char *wf_env = getenv("F3D_WAVEFRONT");
@@ -824,6 +843,142 @@ void resolve(f3d_session &s, uint32_t frames, uint8_t *d_rgba, float *d_albedo, 
     hip_check(launch_resolve(R, s.stream), "resolve kernel");
 }
 
+// A new render on a live session under another sun / seed / exposure / IBL intensity / frame budget: the descriptor's
+// re-armable members replaced, validated and turned into uniforms by the create's own code (validate_desc,
+// fill_uniforms), then k_rearm on the session stream behind everything enqueued so far.  Nothing is allocated, nothing
+// waits for the device.  A refused descriptor leaves the session as it was.
+void rearm(f3d_session &s, const f3d_session_rearm_desc &r) {
+    if (r.struct_size != sizeof(f3d_session_rearm_desc))
+        fail(F3D_STATUS_VALUE, "f3d_session_rearm_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
+             "was built against another revision of f3d_terrain_pt.h", r.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_rearm_desc));
+    if (s.peer[0].connected || s.peer[1].connected)
+        fail(F3D_STATUS_VALUE, "a session with peer halos cannot be re-armed: the frame counters its neighbours poll only rise");
+    f3d_terrain_ref_desc d = s.desc;
+    d.sun_azimuth_deg = r.sun_azimuth_deg;
+    d.sun_elevation_deg = r.sun_elevation_deg;
+    d.sun_intensity = r.sun_intensity;
+    for (int c = 0; c < 3; c++) d.sun_color[c] = r.sun_color[c];
+    d.exposure = r.exposure;
+    d.env_intensity = r.env_intensity;
+    d.seed = r.seed;
+    d.max_frames = r.max_frames;
+    d.min_frames = r.min_frames;
+    d.variance_threshold = r.variance_threshold;
+    d.observer_latitude_deg = r.observer_latitude_deg;
+    d.observer_longitude_deg = r.observer_longitude_deg;
+    d.pressure_mbar = r.pressure_mbar;
+    d.temperature_c = r.temperature_c;
+    validate_desc(d);
+    FrameParams U{};
+    const bool require_valid = fill_uniforms(d, U);
+    // (camera, DEM transform, spacing and spp are the create's: fill_uniforms gives them the same bits again)
+    FrameParams &P = s.params;
+    P.cam = U.cam;
+    P.light = U.light;
+    P.terrain.inv_two_r_prime = U.terrain.inv_two_r_prime;
+    P.terrain.curvature_enabled = U.terrain.curvature_enabled;
+    P.env.intensity = U.env.intensity;
+    P.same_sun = same_sun_of(P);
+    if (s.aether.enabled) aether_sun_terms(s.aether, d);
+    s.require_valid_reservoirs = require_valid;
+    s.desc = d;
+
+    join_bands(s);  // (the session stream after every band launch so far: the clears follow the last frame's kernels)
+    P.band_begin = s.row_begin;
+    P.band_end = s.row_end;
+    P.frame_index = 0;
+    P.trace_first = 0u;
+    P.res_in = s.res[1];
+    P.res_out = s.res[0];
+    P.collect_stats = 0;
+    P.tile_order = nullptr;
+    P.tile_cost = nullptr;
+    RearmParams R{};
+    R.frame = P;
+    R.depth = s.depth;
+    R.res[0] = s.res[0];
+    R.res[1] = s.res[1];
+    R.tile_cost = s.tile_cost;
+    R.tiles = s.tile_cost ? frame_tile_count(P, nullptr) : 0u;
+    hip_check(launch_rearm(R, s.stream), "re-arm kernel");
+    // host-side frame state as a new session has it
+    s.cost_frame = s.order_frame = -1;
+    s.rendered = false;
+    s.trace_first = -1;
+    s.trace_count = 0;
+    for (auto &b : s.bands) {
+        b.last = -1;
+        b.unjoined = false;
+    }
+}
+
+// The accumulation loop of a whole-image session up to the readback (render_terrain.rs:1123-1404): windows of frames
+// until converged or capped, the final resolve (and AETHER post), the copies into the caller's buffers.  Everything of
+// f3d_terrain_ref_out but setup_seconds.
+void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
+    if (s.row_begin != 0u || s.row_end != s.height)
+        fail(F3D_STATUS_VALUE, "f3d_session_render needs a whole-image session (this one owns rows [%u, %u) of %u)", s.row_begin,
+             s.row_end, s.height);
+    if (s.rendered) fail(F3D_STATUS_VALUE, "this session has rendered since its create or last re-arm: re-arm it (f3d_session_rearm) first");
+    s.rendered = true;
+    const f3d_terrain_ref_desc &desc = s.desc;
+    // accumulate until converged or capped, render_terrain.rs:1123-1244.  The reference
+    // checks after every frame whether a 32-frame window just closed; here whole windows
+    // are enqueued without touching the host and only the closing frame reports.
+    uint32_t frames = 0;
+    float variance = INFINITY;
+    bool converged = false;
+    const double t_loop = now_s();
+    while (frames < desc.max_frames) {
+        uint32_t stop = (frames / kWelfordWindow + 1u) * kWelfordWindow;
+        if (stop > desc.max_frames) stop = desc.max_frames;
+        enqueue_range(s, frames, stop - frames, true);
+        frames = stop;
+        const uint32_t n_window = ((frames - 1u) % kWelfordWindow) + 1u;
+        if (n_window >= 2u) {
+            float m2 = 0.0f;
+            int32_t nonfinite = 0;
+            char e2[256];
+            if (f3d_session_window_stats(&s, &m2, &nonfinite, e2, sizeof(e2)) != 0) fail(F3D_STATUS_DEVICE, "%s", e2);
+            if (nonfinite) fail(F3D_STATUS_RENDER, "terrain PT produced non-finite variance (NaN in accumulation)");
+            variance = f_max(0.0f, m2 / ((float)n_window - 1.0f));
+            if (frames >= desc.min_frames && variance < desc.variance_threshold) {
+                converged = true;
+                break;
+            }
+        }
+    }
+    hip_check(hipStreamSynchronize(s.stream), "loop sync");
+    out->loop_seconds = now_s() - t_loop;
+    out->frames = frames;
+    out->variance = variance;
+    out->converged = converged ? 1 : 0;
+    if (!converged)
+        fail(F3D_STATUS_RENDER,
+             "terrain PT did not converge: per-pixel luminance variance %s over the last %u-frame window after "
+             "%u frames (threshold %s); raise max_frames or simplify the scene \xe2\x80\x94 refusing to return a "
+             "fake reference",
+             rust_exp(variance, 3).c_str(), kWelfordWindow, frames, rust_exp(desc.variance_threshold, 1).c_str());
+
+    const double t_read = now_s();
+    int32_t any_valid = 0;
+    char e2[256];
+    const int rc = f3d_session_resolve(&s, frames, out->rgba, out->albedo, out->normal, out->depth, &any_valid, e2, sizeof(e2));
+    if (rc != 0) fail(rc, "%s", e2);
+    if (s.require_valid_reservoirs && !any_valid)
+        fail(F3D_STATUS_RENDER,
+             "terrain PT ReSTIR reuse chain produced no valid reservoirs for a sun-lit scene \xe2\x80\x94 "
+             "temporal/spatial reuse is broken");
+    out->readback_seconds = now_s() - t_read;
+    out->gpu_resource_bytes = s.mem.device_bytes;
+    out->minmax_pyramid_bytes = s.tables.bytes;
+    out->peak_host_visible_bytes = s.mem.host_visible_peak;
+    // budget guardrail on the host-visible peak, render_terrain.rs:1397-1404
+    if (out->peak_host_visible_bytes > s.budget)
+        fail(F3D_STATUS_RENDER, "terrain PT exceeded the host-visible budget: peak %llu > limit %llu",
+             (unsigned long long)out->peak_host_visible_bytes, (unsigned long long)s.budget);
+}
+
 }  // namespace
 
 #include "f3d_host_halo.h"  // peer halos: the pull kernel, the batch enqueue and their C ABI
@@ -1121,6 +1276,48 @@ int f3d_session_fingerprint(f3d_session *s, uint64_t *out, uint32_t count) {
     }
 }
 
+int f3d_session_rearm(f3d_session *s, const f3d_session_rearm_desc *desc, char *err, size_t errlen) {
+    return c_abi(err, errlen, [&] {
+        DeviceGuard g(checked(s).device);
+        if (!desc) fail(F3D_STATUS_VALUE, "null re-arm descriptor");
+        rearm(*s, *desc);
+    });
+}
+
+int f3d_session_render(f3d_session *s, f3d_terrain_ref_out *out, char *err, size_t errlen) {
+    return c_abi(err, errlen, [&] {
+        DeviceGuard g(checked(s).device);
+        if (!out) fail(F3D_STATUS_VALUE, "null output record");
+        const double t_setup = now_s();
+        hip_check(hipStreamSynchronize(s->stream), "setup sync");  // (the G-buffer or re-arm pass still in flight)
+        out->setup_seconds = now_s() - t_setup;
+        render_loop(*s, out);
+    });
+}
+
+// Diagnostics: content hashes of the per-pixel ray certificates (f3d_cone.h) -- out[0] the sun rays', out[1] the primary
+// rays' (0 for a buffer the build leaves out).  Synchronises.
+int f3d_session_certificates(f3d_session *s, uint64_t out[2]) {
+    if (!s || !out) return F3D_STATUS_VALUE;
+    try {
+        DeviceGuard guard(s->device);
+        join_bands(*s);
+        hip_check(hipStreamSynchronize(s->stream), "certificates");
+        const size_t px = (size_t)s->rows * s->width;
+        auto dev = [&](const void *ptr, size_t bytes) -> uint64_t {
+            if (!ptr || !bytes) return 0ull;
+            std::vector<uint8_t> host(bytes);
+            hip_check(hipMemcpy(host.data(), ptr, bytes, hipMemcpyDeviceToHost), "certificate download");
+            return hash_bytes(host.data(), bytes, 0x243F6A8885A308D3ull);
+        };
+        out[0] = dev(s->params.sun_clear, px * sizeof(float2));
+        out[1] = dev(s->params.primary_start, px * sizeof(uint2));
+        return F3D_STATUS_OK;
+    } catch (...) {
+        return F3D_STATUS_DEVICE;
+    }
+}
+
 int f3d_session_debug_wave_times(f3d_session *s, void *device_buffer) {
 #if defined(F3D_WAVE_TIMES)
     if (!s) return F3D_STATUS_VALUE;
@@ -1148,62 +1345,7 @@ int f3d_terrain_ref_render(const f3d_terrain_ref_desc *desc, f3d_terrain_ref_out
         session_init(*s, *desc, &one_shot);
         hip_check(hipStreamSynchronize(s->stream), "setup sync");
         out->setup_seconds = now_s() - t_setup;
-
-        // accumulate until converged or capped, render_terrain.rs:1123-1244.  The reference
-        // checks after every frame whether a 32-frame window just closed; here whole windows
-        // are enqueued without touching the host and only the closing frame reports.
-        uint32_t frames = 0;
-        float variance = INFINITY;
-        bool converged = false;
-        const double t_loop = now_s();
-        while (frames < desc->max_frames) {
-            uint32_t stop = (frames / kWelfordWindow + 1u) * kWelfordWindow;
-            if (stop > desc->max_frames) stop = desc->max_frames;
-            enqueue_range(*s, frames, stop - frames, true);
-            frames = stop;
-            const uint32_t n_window = ((frames - 1u) % kWelfordWindow) + 1u;
-            if (n_window >= 2u) {
-                float m2 = 0.0f;
-                int32_t nonfinite = 0;
-                char e2[256];
-                if (f3d_session_window_stats(s, &m2, &nonfinite, e2, sizeof(e2)) != 0) fail(F3D_STATUS_DEVICE, "%s", e2);
-                if (nonfinite) fail(F3D_STATUS_RENDER, "terrain PT produced non-finite variance (NaN in accumulation)");
-                variance = f_max(0.0f, m2 / ((float)n_window - 1.0f));
-                if (frames >= desc->min_frames && variance < desc->variance_threshold) {
-                    converged = true;
-                    break;
-                }
-            }
-        }
-        hip_check(hipStreamSynchronize(s->stream), "loop sync");
-        out->loop_seconds = now_s() - t_loop;
-        out->frames = frames;
-        out->variance = variance;
-        out->converged = converged ? 1 : 0;
-        if (!converged)
-            fail(F3D_STATUS_RENDER,
-                 "terrain PT did not converge: per-pixel luminance variance %s over the last %u-frame window after "
-                 "%u frames (threshold %s); raise max_frames or simplify the scene \xe2\x80\x94 refusing to return a "
-                 "fake reference",
-                 rust_exp(variance, 3).c_str(), kWelfordWindow, frames, rust_exp(desc->variance_threshold, 1).c_str());
-
-        const double t_read = now_s();
-        int32_t any_valid = 0;
-        char e2[256];
-        rc = f3d_session_resolve(s, frames, out->rgba, out->albedo, out->normal, out->depth, &any_valid, e2, sizeof(e2));
-        if (rc != 0) fail(rc, "%s", e2);
-        if (s->require_valid_reservoirs && !any_valid)
-            fail(F3D_STATUS_RENDER,
-                 "terrain PT ReSTIR reuse chain produced no valid reservoirs for a sun-lit scene \xe2\x80\x94 "
-                 "temporal/spatial reuse is broken");
-        out->readback_seconds = now_s() - t_read;
-        out->gpu_resource_bytes = s->mem.device_bytes;
-        out->minmax_pyramid_bytes = s->tables.bytes;
-        out->peak_host_visible_bytes = s->mem.host_visible_peak;
-        // budget guardrail on the host-visible peak, render_terrain.rs:1397-1404
-        if (out->peak_host_visible_bytes > s->budget)
-            fail(F3D_STATUS_RENDER, "terrain PT exceeded the host-visible budget: peak %llu > limit %llu",
-                 (unsigned long long)out->peak_host_visible_bytes, (unsigned long long)s->budget);
+        render_loop(*s, out);
     } catch (const Failure &f) {
         rc = report(f, err, errlen);
     } catch (const std::exception &e) {

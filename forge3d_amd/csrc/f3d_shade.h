@@ -999,6 +999,14 @@ F3D_HD float frame_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, Pending
 }
 
 // ---- G-buffer + frame-0 AOVs: unjittered centre ray (:583-609, :619-644) ---------------
+// The sun-ray certificate of a pixel whose centre ray hit something (kind != 0) at p with normal n, parameter t: written
+// by the G-buffer pass and, for a new sun over the same G-buffer, by the re-arm pass (rearm_certificate) -- one copy.
+F3D_HD float2 sun_certificate(const FrameParams &P, uint32_t kind, V3 p, V3 n, float t) {
+    float2 c = float2{3.0e38f, 0.0f};
+    if (kind != 0u) c = float2{sun_clear_from(P, along(p, 1e-3f, n), t), t};
+    return c;
+}
+
 template <class Pending>
 F3D_HD void gbuffer_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, float4 *gbuffer_n, float *depth,
                           Pending &pend) {
@@ -1009,11 +1017,7 @@ F3D_HD void gbuffer_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, float4
         P.primary_start[lp] = uint2{f_bits(ps.t_clear), ps.level};
     }
     const SurfaceHit hit = closest_hit(P, P.cam.origin, 1e-3f, rd, 1e30f, pend);
-    if (P.sun_clear) {
-        float2 c = float2{3.0e38f, 0.0f};
-        if (hit.kind != 0u) c = float2{sun_clear_from(P, along(hit.p, 1e-3f, hit.n), hit.t), hit.t};
-        P.sun_clear[lp] = c;
-    }
+    if (P.sun_clear) P.sun_clear[lp] = sun_certificate(P, hit.kind, hit.p, hit.n, hit.t);
     if (hit.kind != 0u) {
         gbuffer_n[lp] = float4{hit.n.x, hit.n.y, hit.n.z, (float)hit.kind};
         depth[lp] = hit.t;
@@ -1021,6 +1025,24 @@ F3D_HD void gbuffer_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, float4
         gbuffer_n[lp] = float4{0.0f, 0.0f, 1.0f, 0.0f};
         depth[lp] = f_from_bits(0x7fc00000u);
     }
+}
+
+// ---- re-arm of a live session (f3d_session_rearm): the sun certificate of a new sun without tracing the camera ray ----
+// closest_hit leaves p = along(cam.origin, t, d) for the unjittered centre ray d = camera_dir(cam, gx, gy, 0, 0), and the
+// G-buffer pass stores t in depth and (n, kind) in gbuffer_n exactly: the certificate's origin comes back bit for bit.
+F3D_HD void rearm_certificate(const FrameParams &P, uint32_t gx, uint32_t gy, const float4 *gbuffer_n, const float *depth) {
+    if (!P.sun_clear) return;
+    const size_t lp = (size_t)(gy - P.row_begin) * P.cam.width + gx;
+    const float4 g = gbuffer_n[lp];
+    const uint32_t kind = (uint32_t)g.w;
+    V3 p = V3{0.0f, 0.0f, 0.0f}, n = V3{0.0f, 0.0f, 0.0f};
+    float t = 0.0f;
+    if (kind != 0u) {
+        t = depth[lp];
+        n = V3{g.x, g.y, g.z};
+        p = along(P.cam.origin, t, camera_dir(P.cam, gx, gy, 0.0f, 0.0f));
+    }
+    P.sun_clear[lp] = sun_certificate(P, kind, p, n, t);
 }
 
 // ---- final resolve: last spatial pass + validity (render_terrain.rs:1313-1337),

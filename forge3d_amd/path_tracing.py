@@ -184,20 +184,82 @@ def hybrid_render_terrain_reference(
     if getattr(_NATIVE, "hybrid_render_terrain_reference", None) is None:
         raise RuntimeError("hybrid_render_terrain_reference requires the native forge3d module with GPU support")
 
+    request, sun, keywords = _prepare(heightmap, width, height, camera, options)
+    result = _NATIVE.hybrid_render_terrain_reference(request.dem, request.width, request.height, request.camera,
+                                                     **keywords)
+    return _with_sun(result, sun)
+
+
+def _prepare(heightmap, width, height, camera, options: dict):
+    """The wrapper's checks, in its order, and the native keyword set of one call: (request, sun, keywords)."""
     request = _Request(np.ascontiguousarray(heightmap, dtype=np.float32), int(width), int(height),
                        dict(camera or {}), options)
     for is_bad, message in _RULES:
         if is_bad(request):
             raise ValueError(message(request))
-    request.sun_rgb = _parse_sun_color(sun_color)
+    request.sun_rgb = _parse_sun_color(options["sun_color"])
     sun = _SunResolution.of(options)
     _coerce_scene_arrays(request)
 
     values = {**options, **sun.values, "sun_color": request.sun_rgb, "env_map": request.env,
               "mesh_vertices": request.mesh_v, "mesh_indices": request.mesh_i}
     keywords = {name: convert(values[name]) for name, convert in _NATIVE_KEYWORDS}
-    result = _NATIVE.hybrid_render_terrain_reference(request.dem, request.width, request.height, request.camera,
-                                                     **keywords)
+    return request, sun, keywords
+
+
+def _with_sun(result: dict, sun: _SunResolution) -> dict:
     result.update(sun_source=sun.source, solar_azimuth_deg=float(sun.values["sun_azimuth_deg"]),
                   solar_elevation_deg=float(sun.values["sun_elevation_deg"]))
     return result
+
+
+# ---- a sequence of renders of one scene under changing suns: one live session, re-armed per frame ----------------------
+# per-frame keys a live session can change (forge3d_amd.session.TerrainSession.rearm); solar_time resolves to some of them
+SEQUENCE_FRAME_KEYS = ("sun_azimuth_deg", "sun_elevation_deg", "solar_time", "sun_intensity", "sun_color", "env_intensity",
+                       "seed", "max_frames", "min_frames", "variance_threshold", "observer_latitude_deg",
+                       "observer_longitude_deg", "pressure_mbar", "temperature_c")
+
+
+def render_terrain_sequence(heightmap: "np.ndarray", width: int, height: int, camera: "dict | None" = None, *,
+                            frames: "Sequence[Mapping[str, Any]]", **common):
+    """Generator: item i equals ``hybrid_render_terrain_reference(heightmap, width, height, camera, **common, **frames[i])``.
+
+    ``common`` takes the wrapper's keywords; ``frames[i]`` only keys a live session can change (SEQUENCE_FRAME_KEYS: the
+    sun by angles or ``solar_time``, intensity, colour, IBL intensity, seed, frame budget, observer / air for the
+    refraction).  Every frame is checked by the wrapper's own rules before any device work; then ONE session renders the
+    whole sequence, re-armed between frames (f3d_session_rearm: no new tables, allocations or G-buffer pass).
+    """
+    import inspect
+
+    from .session import TerrainSession
+
+    signature = inspect.signature(hybrid_render_terrain_reference)
+    defaults = {name: p.default for name, p in signature.parameters.items() if p.kind is inspect.Parameter.KEYWORD_ONLY}
+    for name in common:
+        if name not in defaults:
+            raise TypeError(f"render_terrain_sequence() got an unexpected keyword argument {name!r}")
+    frames = [dict(f) for f in frames]
+    for i, frame in enumerate(frames):
+        for key in frame:
+            if key not in SEQUENCE_FRAME_KEYS:
+                raise ValueError(f"frames[{i}] sets {key!r}, which a live session cannot change (per-frame keys: "
+                                 f"{', '.join(SEQUENCE_FRAME_KEYS)}); render it with hybrid_render_terrain_reference")
+    if getattr(_NATIVE, "hybrid_render_terrain_reference", None) is None:
+        raise RuntimeError("hybrid_render_terrain_reference requires the native forge3d module with GPU support")
+    calls = [_prepare(heightmap, width, height, camera, {**defaults, **common, **frame}) for frame in frames]
+    if not calls:
+        return
+    request, _, first = calls[0]
+    native = dict(first)
+    native.pop("certificate")
+    native["atmosphere"] = _NATIVE_MODULE._resolve_atmosphere(native["atmosphere"])
+    # one-shot calls size frames in flight automatically: so does the session (same byte counts in the result)
+    session = TerrainSession(request.dem, request.width, request.height, request.camera,
+                             frames_in_flight=_NATIVE_MODULE.FRAMES_IN_FLIGHT_AUTO, **native)
+    try:
+        for i, (_, sun, keywords) in enumerate(calls):
+            if i:
+                session.rearm(**{key: keywords[key] for key in TerrainSession.REARMABLE if key in keywords})
+            yield _with_sun(session.render(), sun)
+    finally:
+        session.close()

@@ -55,6 +55,15 @@ class TerrainSession:
             self._handle = C.c_void_p(None)
             _native.raise_status(rc, err.value.decode("utf-8", "replace"))
         self.width, self.height = int(width), int(height)
+        # what rearm() keeps when a value is not given: the descriptor's re-armable members as the library holds them
+        self._armed = {"sun_azimuth_deg": float(desc.sun_azimuth_deg), "sun_elevation_deg": float(desc.sun_elevation_deg),
+                       "sun_intensity": float(desc.sun_intensity), "sun_color": tuple(float(c) for c in desc.sun_color),
+                       "exposure": float(desc.exposure), "env_intensity": float(desc.env_intensity), "seed": int(desc.seed),
+                       "max_frames": int(desc.max_frames), "min_frames": int(desc.min_frames),
+                       "variance_threshold": float(desc.variance_threshold),
+                       "observer_latitude_deg": float(desc.observer_latitude_deg),
+                       "observer_longitude_deg": float(desc.observer_longitude_deg),
+                       "pressure_mbar": float(desc.pressure_mbar), "temperature_c": float(desc.temperature_c)}
         self.row_begin = int(row_begin)
         self.row_end = int(row_end) or int(height)
         self.rows = self.row_end - self.row_begin
@@ -82,6 +91,57 @@ class TerrainSession:
     def _check(self, rc):
         if rc != 0:
             _native.raise_status(rc, self._err.value.decode("utf-8", "replace"))
+
+    # -- re-arm: another render on this session ---------------------------------------
+    REARMABLE = ("sun_azimuth_deg", "sun_elevation_deg", "sun_intensity", "sun_color", "exposure", "env_intensity", "seed",
+                 "max_frames", "min_frames", "variance_threshold", "observer_latitude_deg", "observer_longitude_deg",
+                 "pressure_mbar", "temperature_c")
+
+    def rearm(self, *, sun_azimuth_deg=None, sun_elevation_deg=None, sun_intensity=None, sun_color=None, exposure=None,
+              env_intensity=None, seed=None, max_frames=None, min_frames=None, variance_threshold=None,
+              observer_latitude_deg=None, observer_longitude_deg=None, pressure_mbar=None, temperature_c=None):
+        """Make the next frames a new render under another sun / seed / exposure / IBL intensity / frame budget (None keeps
+        the current value): what a new session with these values renders, without its set-up.  Asynchronous on the
+        session stream, behind everything enqueued so far; a refused value leaves the session as it was."""
+        given = dict(locals())
+        given.pop("self")
+        values = {k: (self._armed[k] if v is None else v) for k, v in given.items()}
+        if sun_color is not None:
+            values["sun_color"] = tuple(_native._extract_sun_color(sun_color))
+        for key in ("seed", "max_frames", "min_frames"):
+            if int(values[key]) < 0:
+                raise OverflowError("can't convert negative int to unsigned")
+        r = _native.RearmDesc()
+        r.struct_size = C.sizeof(_native.RearmDesc)
+        for key in ("sun_azimuth_deg", "sun_elevation_deg", "sun_intensity", "exposure", "env_intensity", "variance_threshold",
+                    "observer_latitude_deg", "observer_longitude_deg", "pressure_mbar", "temperature_c"):
+            setattr(r, key, float(values[key]))
+        r.sun_color = _native._f3(values["sun_color"])
+        r.seed, r.max_frames, r.min_frames = int(values["seed"]), int(values["max_frames"]), int(values["min_frames"])
+        self._check(self._lib.f3d_session_rearm(self._handle, C.byref(r), self._err, len(self._err)))
+        # (as the library holds them: float32)
+        self._armed = {k: (tuple(float(c) for c in r.sun_color) if k == "sun_color" else type(self._armed[k])(getattr(r, k)))
+                       for k in self._armed}
+
+    def render(self) -> dict:
+        """The accumulation / convergence loop, resolve and readback of hybrid_render_terrain_reference on this (whole-image)
+        session; the same dict, with the frame budget of the create or of the last rearm()."""
+        h, w = self.height, self.width
+        rgba = np.zeros((h, w, 4), np.uint8)
+        alb = np.zeros((h, w, 3), np.float32)
+        nrm = np.zeros((h, w, 3), np.float32)
+        dep = np.zeros((h, w), np.float32)
+        o = _native.Out()
+        o.rgba, o.albedo, o.normal, o.depth = rgba.ctypes.data, alb.ctypes.data, nrm.ctypes.data, dep.ctypes.data
+        self._check(self._lib.f3d_session_render(self._handle, C.byref(o), self._err, len(self._err)))
+        return _native.result_dict(rgba, alb, nrm, dep, o, self._armed["sun_azimuth_deg"], self._armed["sun_elevation_deg"])
+
+    def certificates(self) -> dict:
+        """Diagnostics (synchronises): content hashes of the sun-ray and primary-ray certificates."""
+        out = (C.c_uint64 * 2)()
+        if self._lib.f3d_session_certificates(self._handle, out) != 0:
+            raise RuntimeError("f3d_session_certificates failed")
+        return {"sun_clear": int(out[0]), "primary_start": int(out[1])}
 
     # -- stepping ---------------------------------------------------------------------
     def enqueue_frames(self, first_frame: int, count: int, collect_stats: bool = False):

@@ -781,3 +781,57 @@ class SmokeSequence:
             setattr(self.domain, name, self.state[name].cpu().numpy())
         self.domain.time_seconds, self.domain.frame_index = self.time_seconds, self.frame_index
         return self.domain
+
+
+class TerrainSunProvider:
+    """``base_provider`` of ``SmokeSequence.frames``: a terrain render per frame, resolved on the device into the frame's
+    base image, from ONE live terrain session re-armed per frame (TerrainSession.rearm: the sun and seed of the frame,
+    no new session's set-up).  Made by ``terrain_sun_provider``; close() releases the session."""
+
+    def __init__(self, heightmap, camera, sun_path, frames, render):
+        self._dem, self._camera, self._sun_path, self._frames, self._render = heightmap, camera, sun_path, int(frames), dict(render)
+        if self._frames < 1:
+            raise ValueError("frames must be >= 1")
+        for key in ("max_frames", "min_frames", "stream", "row_begin", "row_end"):
+            if key in self._render:
+                raise ValueError(f"terrain_sun_provider sets {key!r} itself")
+        self.session = None
+        self._stream = None
+
+    def __call__(self, index, base, stream):
+        import torch
+
+        from .session import TerrainSession
+
+        sun = dict(self._sun_path(int(index)))
+        for key in sun:
+            if key not in TerrainSession.REARMABLE or key in ("max_frames", "min_frames"):
+                raise ValueError(f"sun_path({index}) sets {key!r}, which a live session cannot change per frame")
+        height, width = int(base.shape[0]), int(base.shape[1])
+        if self.session is None:  # (on a stream of the provider's: ordered against the caller's stream below)
+            self._stream = torch.cuda.Stream(device=base.device)
+            self._stream.wait_stream(stream)
+            self.session = TerrainSession(self._dem, width, height, self._camera, stream=self._stream.cuda_stream,
+                                          max_frames=self._frames, min_frames=self._frames, **{**self._render, **sun})
+        else:
+            if (self.session.width, self.session.height) != (width, height):
+                raise ValueError(f"base image is {width}x{height}, the provider's session renders "
+                                 f"{self.session.width}x{self.session.height}")
+            self._stream.wait_stream(stream)  # (behind the composite that read the frame before's base)
+            self.session.rearm(**sun)
+        self.session.enqueue_frames(0, self._frames)
+        self.session.resolve_device(self._frames, d_rgba=base.data_ptr())
+        stream.wait_stream(self._stream)
+
+    def close(self):
+        if self.session is not None:
+            self.session.close()
+            self.session = None
+
+
+def terrain_sun_provider(heightmap, camera, *, sun_path, frames: int = 8, **render) -> TerrainSunProvider:
+    """A ``base_provider`` for ``SmokeSequence.frames(..., base_provider=...)``: frame i's base image is a terrain render of
+    `frames` accumulation frames under ``sun_path(i)`` (a mapping of re-armable keys, e.g. ``{"sun_azimuth_deg": a}``), from
+    one session created at the first frame and re-armed for every later one.  ``render``: TerrainSession keywords (spacing,
+    exaggeration, spp, seed, memory_budget_bytes, kernel_variant, ...).  The images equal those of a new session per frame."""
+    return TerrainSunProvider(heightmap, camera, sun_path, frames, render)

@@ -306,6 +306,37 @@ int f3d_session_resolve_device(f3d_session *session, uint32_t frames, void *d_rg
  * device time is NOT in it: the call returns with them in flight).  [3] and [4] are 0 for a DEM the scene cache holds. */
 #define F3D_SETUP_PHASES 8
 int f3d_session_setup_ms(f3d_session *session, double *out, uint32_t count);
+/* ---- re-arm: another render on a live session ---------------------------------------------------------------
+ * What a new sun, seed, exposure, IBL intensity or frame budget changes, without a new session: the uniforms, the
+ * per-pixel sun-ray certificates (recomputed from the resident G-buffer, the camera rays are not traced again), the
+ * AETHER record's sun terms, and the per-render state (accumulation, Welford, both reservoir buffers with their halo
+ * rows -- caller-owned ones included --, head records, tile costs, stats), cleared as a new session has them.  Camera,
+ * DEM, exaggeration, spacing, mesh, environment map, image size, strip rows, spp, earth / refraction model and
+ * atmosphere LUTs stay the session's; observer latitude / longitude, pressure and temperature are re-armable (they
+ * only enter the curvature of the secondary rays).  The next frames render exactly what a new session created with
+ * these values renders.  Added without an ABI version bump (no existing struct or signature changed): a binding
+ * detects the feature by the symbol f3d_session_rearm. */
+typedef struct f3d_session_rearm_desc {
+    uint32_t struct_size; /* = sizeof(f3d_session_rearm_desc) of the caller's header */
+    float sun_azimuth_deg, sun_elevation_deg, sun_intensity;
+    float sun_color[3];
+    float exposure, env_intensity;
+    uint32_t seed, max_frames, min_frames;
+    float variance_threshold;
+    double observer_latitude_deg, observer_longitude_deg, pressure_mbar, temperature_c;
+} f3d_session_rearm_desc;
+/* Validates with the create's code and messages (a refused descriptor leaves the session unchanged and usable), then
+ * enqueues the re-arm pass on the session stream behind everything enqueued so far (band streams included) and
+ * returns without waiting: frames, a resolve, a re-arm and the next frames may be enqueued back to back.  Allocates
+ * nothing.  Refused (status 1) for a session with connected peer halos (their frame counters only rise). */
+int f3d_session_rearm(f3d_session *session, const f3d_session_rearm_desc *desc, char *err, size_t errlen);
+/* The accumulation / convergence-window / resolve / readback loop of f3d_terrain_ref_render on a live whole-image
+ * session (f3d_terrain_ref_render is create + this loop + destroy): the same outputs, timings and errors; the frame
+ * budget is the create's or the last re-arm's.  Blocking.  Once per create or re-arm (a second call without a re-arm in
+ * between is refused, status 1: the accumulation it would continue is spent). */
+int f3d_session_render(f3d_session *session, f3d_terrain_ref_out *out, char *err, size_t errlen);
+/* Diagnostics (synchronises): content hashes of the sun-ray (out[0]) and primary-ray (out[1]) certificates. */
+int f3d_session_certificates(f3d_session *session, uint64_t out[2]);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);

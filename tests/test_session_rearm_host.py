@@ -1,0 +1,199 @@
+"""Re-arm of a live terrain session (f3d_session_rearm), the parts that need no GPU.
+
+* The re-arm pass's pixel body (f3d_shade.h rearm_certificate, run per pixel by k_rearm) rebuilds every sun-ray certificate
+  of a new sun from a G-buffer made under another sun, bit for bit what the G-buffer pass writes under the new sun: 240
+  random scenes (DEMs, cameras, spacings, sun pairs including the zenith and suns below the horizon, curvature on / off,
+  meshes walked binary and four wide), through the product's headers compiled for the host (tests/rearm_host).
+* render_terrain_sequence refuses what a live session cannot change, with the wrapper's exception types and messages,
+  before the device is touched.
+* The header, the ctypes table and the descriptor's layout.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import scenes
+
+ROOT = Path(__file__).resolve().parent.parent
+HARNESS = ROOT / "tests" / "rearm_host" / "rearm_harness.cpp"
+SCENES = 240
+
+
+@pytest.fixture(scope="module")
+def harness():
+    out = Path(tempfile.mkdtemp(prefix="f3d_rearm_host_")) / "librearm_host.so"
+    # (the emulator's flags, tests/emul/emul.py)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
+                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
+    lib = C.CDLL(str(out))
+    lib.rearm_check.restype = C.c_int
+    return lib
+
+
+def _desc(dem, size, cam, kw):
+    from forge3d_amd import _native
+
+    k = dict(kw)
+    k.setdefault("env_map", None)
+    k.setdefault("mesh_vertices", None)
+    k.setdefault("mesh_indices", None)
+    return _native.make_desc(dem, size[0], size[1], cam, k["spacing"], k["exaggeration"], k["albedo"], k["sun_azimuth_deg"],
+                             k["sun_elevation_deg"], k["sun_intensity"], k["env_map"], k["env_intensity"], k["mesh_vertices"],
+                             k["mesh_indices"], k["spp"], k["max_frames"], k["min_frames"], k["variance_threshold"], k["seed"],
+                             k.get("sun_color", (1.0, 0.97, 0.92)), k.get("observer_latitude_deg", 0.0),
+                             k.get("observer_longitude_deg", 0.0), k["earth_model"], k.get("sphere_radius_m", 6371008.8),
+                             k["refraction_model"], k.get("refraction_k", 0.13), k.get("pressure_mbar", 1013.25),
+                             k.get("temperature_c", 15.0))
+
+
+def _scene_pair(i):
+    """Scene i under sun A and sun B (everything else equal but what a re-arm may change)."""
+    dem, size, cam, kw = scenes.random_scene(9100 + i)
+    rng = np.random.default_rng(77_000 + i)
+    if i % 2 == 0 and "mesh_vertices" not in kw:  # half the scenes carry a mesh
+        span = kw["spacing"][0] * max(dem.shape)
+        relief = kw["exaggeration"] * float(dem.max())
+        kw["mesh_vertices"], kw["mesh_indices"] = scenes.box_city(n_boxes=int(rng.integers(1, 16)), seed=i, span=0.8 * span,
+                                                                  base=0.0, top=max(relief, 1.0))
+    if i % 3 == 0:  # strong curvature: a small sphere
+        kw.update(earth_model="sphere", refraction_model="none", sphere_radius_m=float(kw["spacing"][0] * max(dem.shape) * 3.0))
+    elif i % 3 == 1:
+        kw.update(earth_model="flat", refraction_model="none")  # curvature off
+    elevation = [90.0, -5.0, float(rng.uniform(1, 89)), float(rng.uniform(-20, 0)), float(rng.uniform(30, 89.9))][i % 5]
+    b = dict(kw, sun_azimuth_deg=float(rng.uniform(0, 360)), sun_elevation_deg=elevation, seed=int(rng.integers(0, 2 ** 31)),
+             sun_intensity=float(rng.uniform(0.0, 4.0)), observer_latitude_deg=float(rng.uniform(-80, 80)),
+             pressure_mbar=float(rng.uniform(700, 1050)), temperature_c=float(rng.uniform(-20, 35)))
+    return dem, size, cam, kw, b
+
+
+def test_rearmed_sun_certificates_equal_the_gbuffer_pass_under_the_new_sun(harness):
+    totals = np.zeros(5, np.uint64)
+    meshes = 0
+    for i in range(SCENES):
+        dem, size, cam, a, b = _scene_pair(i)
+        da, ka = _desc(dem, size, cam, a)
+        db, kb = _desc(dem, size, cam, b)
+        out = (C.c_uint64 * 5)()
+        form = 1 + (i // 2) % 2
+        assert harness.rearm_check(C.byref(da), C.byref(db), form, out) == 0, f"scene {i} refused"
+        pixels, hits, bad, gbad, finite = (int(v) for v in out)
+        assert gbad == 0, f"scene {i}: the two G-buffer passes differ ({gbad} pixels)"
+        assert bad == 0, f"scene {i}: {bad} of {pixels} re-armed sun certificates differ from the G-buffer pass's"
+        totals += np.array([pixels, hits, bad, gbad, finite], np.uint64)
+        meshes += a.get("mesh_vertices") is not None
+        del ka, kb
+    pixels, hits, _, _, finite = (int(v) for v in totals)
+    assert meshes >= SCENES // 3
+    assert hits > pixels // 5 and 0 < finite < hits  # the scenes hit terrain, and the certificates say something
+
+
+def test_the_harness_sees_a_stale_certificate(harness):
+    """The comparison can fail: a G-buffer made under sun A and NOT re-armed keeps certificates that differ from sun B's."""
+    dem, size, cam, a, b = _scene_pair(2)
+    b = dict(a, sun_azimuth_deg=a["sun_azimuth_deg"] + 90.0, sun_elevation_deg=12.0)
+    da, ka = _desc(dem, size, cam, a)
+    out = (C.c_uint64 * 5)()
+    # (the same descriptor twice: the re-arm must be a no-op, and the certificates of another sun are another bit pattern)
+    assert harness.rearm_check(C.byref(da), C.byref(da), 2, out) == 0 and int(out[2]) == 0
+    db, kb = _desc(dem, size, cam, b)
+    assert harness.rearm_check(C.byref(db), C.byref(db), 2, out) == 0 and int(out[2]) == 0
+    assert int(out[4]) > 0
+
+
+# ---- render_terrain_sequence: what it refuses, before any device work ----------------------------------------------------
+def _no_device(monkeypatch):
+    from forge3d_amd import _native, session
+
+    def boom(*a, **k):
+        raise AssertionError("the device was touched")
+
+    monkeypatch.setattr(_native, "lib", boom)
+    monkeypatch.setattr(session.TerrainSession, "__init__", boom)
+
+
+@pytest.mark.parametrize("key,value", [("camera", {"origin": (0, 1, 2)}), ("spp", 4), ("width", 64), ("mesh_vertices", np.zeros((3, 3))),
+                                       ("exaggeration", 2.0), ("spacing", (2.0, 2.0)), ("env_map", None), ("atmosphere", None)])
+def test_sequence_refuses_a_key_a_live_session_cannot_change(monkeypatch, key, value):
+    from forge3d_amd.path_tracing import render_terrain_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    frames = [{"sun_azimuth_deg": 10.0}, {"sun_azimuth_deg": 20.0, key: value}]
+    with pytest.raises(ValueError, match=re.escape(f"frames[1] sets {key!r}")):
+        list(render_terrain_sequence(dem, 32, 24, scenes.CAM, frames=frames, **scenes.scene_kwargs(dem)))
+
+
+def _wrapper_error(call):
+    try:
+        call()
+    except AssertionError:  # (got as far as the native call: accepted)
+        return None
+    except Exception as e:  # noqa: BLE001
+        return type(e), str(e)
+    return None
+
+
+def test_sequence_refuses_what_the_wrapper_refuses_with_its_types_and_messages(monkeypatch):
+    from forge3d_amd import path_tracing
+    from forge3d_amd.path_tracing import hybrid_render_terrain_reference, render_terrain_sequence
+
+    _no_device(monkeypatch)
+    monkeypatch.setattr(path_tracing._NATIVE, "hybrid_render_terrain_reference", lambda *a, **k: (_ for _ in ()).throw(AssertionError("rendered")))
+    dem = scenes.golden_dem(8)
+    kw = scenes.scene_kwargs(dem)
+    kw.pop("sun_azimuth_deg"), kw.pop("sun_elevation_deg")
+    when = {"datetime_utc": "2024-06-21T12:00:00Z", "latitude_deg": 46.85, "longitude_deg": -121.76}
+    cases = [
+        ({}, [{"solar_time": when, "sun_azimuth_deg": 10.0}]),                            # solar_time + manual angles
+        ({"observer_latitude_deg": 12.0}, [{"solar_time": when}]),                         # ... + a manual observer
+        ({}, [{"sun_azimuth_deg": 1.0}, {"sun_color": (1.0, -1.0, 0.5)}]),                 # a bad colour in frame 1
+        ({}, [{"sun_azimuth_deg": 1.0}, {"min_frames": 600, "max_frames": 512}]),          # budget order
+        ({}, [{"sun_azimuth_deg": 1.0}, {"sun_color": "red"}]),
+    ]
+    for common, frames in cases:
+        for frame in frames:
+            want = _wrapper_error(lambda: hybrid_render_terrain_reference(dem, 32, 24, scenes.CAM, **{**kw, **common, **frame}))
+            if want is not None:
+                break
+        assert want is not None, (common, frames)
+        with pytest.raises(want[0]) as got:
+            list(render_terrain_sequence(dem, 32, 24, scenes.CAM, frames=frames, **kw, **common))
+        assert str(got.value) == want[1]
+    with pytest.raises(TypeError, match="unexpected keyword argument 'bogus'"):
+        list(render_terrain_sequence(dem, 32, 24, scenes.CAM, frames=[{}], bogus=1, **kw))
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------
+def test_header_and_ctypes_table_declare_the_rearm_entry_points():
+    from forge3d_amd import _native
+
+    header = (ROOT / "include" / "f3d_terrain_pt.h").read_text()
+    names = {n for n, _, _ in _native.ABI}
+    for fn in ("f3d_session_rearm", "f3d_session_render", "f3d_session_certificates"):
+        assert re.search(rf"\b{fn}\s*\(", header), fn
+        assert fn in names, fn
+    assert "#define F3D_ABI_VERSION 6u" in header  # additive: detected by the symbol
+    body = re.search(r"typedef struct f3d_session_rearm_desc \{(.*?)\} f3d_session_rearm_desc;", header, re.S).group(1)
+    assert body.split(";")[0].split() == ["uint32_t", "struct_size"]
+    assert _native.RearmDesc._fields_[0] == ("struct_size", C.c_uint32)
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "f3d_terrain_pt.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", ' \
+          "sizeof(f3d_session_rearm_desc), offsetof(f3d_session_rearm_desc, seed), offsetof(f3d_session_rearm_desc, variance_threshold), " \
+          "offsetof(f3d_session_rearm_desc, temperature_c)); return 0; }\n"
+    with tempfile.TemporaryDirectory() as tmp:
+        c = Path(tmp) / "layout.c"
+        c.write_text(src)
+        exe = Path(tmp) / "layout"
+        subprocess.run(["gcc", "-I", str(ROOT / "include"), str(c), "-o", str(exe)], check=True)
+        got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    R = _native.RearmDesc
+    assert got == [C.sizeof(R), R.seed.offset, R.variance_threshold.offset, R.temperature_c.offset]
+    text = (ROOT / "INTEGRATION.md").read_text()
+    assert "pub struct F3dSessionRearmDesc" in text and "f3d_session_rearm" in text
