@@ -114,6 +114,16 @@ class RearmDesc(C.Structure):
     ]
 
 
+class ReaimDesc(C.Structure):
+    """f3d_session_reaim_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("cam_origin", C.c_float * 3), ("cam_look_at", C.c_float * 3), ("cam_up", C.c_float * 3),
+        ("fov_y_deg", C.c_float),
+        ("arm", RearmDesc),
+    ]
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -148,6 +158,7 @@ ABI = [
     # re-arm of a live session (no ABI version bump: detected by the symbol)
     ("f3d_session_rearm", C.c_int, [C.c_void_p, _P(RearmDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_render", C.c_int, [C.c_void_p, _P(Out), C.c_char_p, C.c_size_t]),
+    ("f3d_session_reaim", C.c_int, [C.c_void_p, _P(ReaimDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
     ("f3d_session_halo", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p), _P(C.c_uint64)]),
@@ -404,6 +415,13 @@ def attach_atmosphere(desc, handle, keep):
     desc.atmosphere = C.addressof(luts)
 
 
+def camera_members(cam):
+    """The camera dict as a descriptor holds it -- (cam_origin, cam_look_at, cam_up, fov_y_deg, exposure) -- with the
+    wrapper's defaults for missing keys: read by make_desc for a new session and by TerrainSession.reaim for a live one."""
+    return (_f3(cam.get("origin", (0.0, 50.0, 120.0))), _f3(cam.get("look_at", (0.0, 0.0, 0.0))),
+            _f3(cam.get("up", (0.0, 1.0, 0.0))), float(cam.get("fov_y", 45.0)), float(cam.get("exposure", 1.0)))
+
+
 def make_desc(heightmap, width, height, cam, spacing, exaggeration, albedo, sun_azimuth_deg, sun_elevation_deg,
               sun_intensity, env_map, env_intensity, mesh_vertices, mesh_indices, spp, max_frames, min_frames,
               variance_threshold, seed, sun_color, observer_latitude_deg, observer_longitude_deg, earth_model,
@@ -424,11 +442,7 @@ def make_desc(heightmap, width, height, cam, spacing, exaggeration, albedo, sun_
     d.spacing_x, d.spacing_z = float(spacing[0]), float(spacing[1])
     d.exaggeration = float(exaggeration)
     d.albedo = _f3(albedo)
-    d.cam_origin = _f3(cam.get("origin", (0.0, 50.0, 120.0)))
-    d.cam_look_at = _f3(cam.get("look_at", (0.0, 0.0, 0.0)))
-    d.cam_up = _f3(cam.get("up", (0.0, 1.0, 0.0)))
-    d.fov_y_deg = float(cam.get("fov_y", 45.0))
-    d.exposure = float(cam.get("exposure", 1.0))
+    d.cam_origin, d.cam_look_at, d.cam_up, d.fov_y_deg, d.exposure = camera_members(cam)
     d.sun_azimuth_deg = float(sun_azimuth_deg)
     d.sun_elevation_deg = float(sun_elevation_deg)
     d.sun_intensity = float(sun_intensity)

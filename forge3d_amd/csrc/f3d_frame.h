@@ -629,10 +629,6 @@ __global__ __launch_bounds__(kWave) void k_merge(const FrameParams P) {
 
 // First prediction of "the merged reservoir is valid" for the frames traced before any merge: the centre ray hit a
 // surface that faces the sun.
-// first sun-direction prediction of a pixel from its G-buffer record (k_trace_init, and k_rearm for a new sun)
-__device__ __forceinline__ uint2 first_head(const FrameParams &P, float4 g) {
-    return uint2{0u, (g.w != 0.0f && dot(V3{g.x, g.y, g.z}, P.light.wi) > 0.0f) ? kHeadPrevValid : 0u};
-}
 __global__ __launch_bounds__(kWave) void k_trace_init(const FrameParams P) {
     uint32_t gx, gy;
     if (!tile_pixel(P, gx, gy)) return;
@@ -733,33 +729,24 @@ __global__ __launch_bounds__(kWave) void k_gbuffer(const FrameParams P, float4 *
 
 // Re-arm of a live session for a new sun / seed / frame budget (f3d_session_rearm): one lane per owned pixel, the
 // G-buffer pass's grid and mapping.  The pixel's sun certificate for the new sun from the resident G-buffer (no camera
-// ray), and the per-render state as a new session's create leaves it before its first frame: accumulation, Welford M2,
-// both reservoir buffers with their halo rows (buffer row r is cleared by the lane of owned row r mod rows), head
-// records (frames in flight: the first sun-direction prediction, as k_trace_init), tile costs, stats, retrace counters.
+// ray), and the per-render state as a new session's create leaves it before its first frame (f3d_shade.h rearm_clear,
+// rearm_head).
 __global__ __launch_bounds__(kWave) void k_rearm(const RearmParams R) {
-    static_assert(sizeof(PackedReservoir) == sizeof(float4), "one 16-byte store clears a reservoir");
     const FrameParams &P = R.frame;
     uint32_t gx, gy;
     if (!tile_pixel(P, gx, gy)) return;
     rearm_certificate(P, gx, gy, P.gbuffer_n, R.depth);
-    const uint32_t W = P.cam.width, row = gy - P.row_begin, rows = P.row_end - P.row_begin;
-    const size_t lp = (size_t)row * W + gx;
-    const float4 zero4 = float4{0.0f, 0.0f, 0.0f, 0.0f};
-    P.accum_mean[lp] = zero4;
-    P.welford_m2[lp] = 0.0f;
-    for (uint32_t r = row; r < rows + 2u * kHaloRows; r += rows) {
-        const size_t i = (size_t)r * W + gx;
-        reinterpret_cast<float4 *>(R.res[0])[i] = zero4;  // (a packed reservoir is one 16-byte record)
-        reinterpret_cast<float4 *>(R.res[1])[i] = zero4;
-    }
-    if (P.head) P.head[lp] = P.trace ? first_head(P, P.gbuffer_n[lp]) : uint2{0u, 0u};
-    if (R.tile_cost && lp < R.tiles) R.tile_cost[lp] = 0u;
-    if (lp == 0u) {
-        for (uint32_t k = 0u; k < 4u; k++) {
-            if (P.stats) P.stats[k] = 0u;
-            if (P.fix_count) P.fix_count[k] = 0u;
-        }
-    }
+    rearm_clear(R, gx, gy);
+    rearm_head(P, gx, gy, P.gbuffer_n[(size_t)(gy - P.row_begin) * P.cam.width + gx]);
+}
+
+// Re-aim of a live session (f3d_session_reaim): the re-arm under a new camera -- k_gbuffer's and k_rearm's work in one
+// launch on their grid (f3d_shade.h reaim_pixel), every sun certificate computed once.
+__global__ __launch_bounds__(kWave) void k_reaim(const RearmParams R) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+    LdsPending pend = make_pending(lds, R.frame.terrain);
+    uint32_t gx, gy;
+    if (tile_pixel(R.frame, gx, gy)) reaim_pixel(R, gx, gy, pend);
 }
 
 __global__ __launch_bounds__(kWave) void k_resolve(const ResolveParams R) {

@@ -119,6 +119,7 @@ struct f3d_session {
     // (f3d_session_rearm) starts from and what f3d_session_render's loop reads its frame budget from
     f3d_terrain_ref_desc desc{};
     bool rendered = false;  // f3d_session_render has run since the create or the last re-arm (its state is spent)
+    double reaim_seconds = 0.0;  // host time of a re-aim call since the last f3d_session_render: part of its setup_seconds
     uint64_t budget = 0;
     // band pipelining (f3d_session_opts.bands): horizontal bands of the strip, their streams and events
     struct Band {
@@ -843,16 +844,22 @@ void resolve(f3d_session &s, uint32_t frames, uint8_t *d_rgba, float *d_albedo, 
     hip_check(launch_resolve(R, s.stream), "resolve kernel");
 }
 
-// A new render on a live session under another sun / seed / exposure / IBL intensity / frame budget: the descriptor's
-// re-armable members replaced, validated and turned into uniforms by the create's own code (validate_desc,
-// fill_uniforms), then k_rearm on the session stream behind everything enqueued so far.  Nothing is allocated, nothing
-// waits for the device.  A refused descriptor leaves the session as it was.
-void rearm(f3d_session &s, const f3d_session_rearm_desc &r) {
+// A new render on a live session under another sun / seed / exposure / IBL intensity / frame budget, and (re-aim: cam
+// given) another camera: the descriptor's re-armable members replaced, validated and turned into uniforms by the
+// create's own code (validate_desc, fill_uniforms), then k_rearm -- or, for a new camera, k_reaim -- on the session
+// stream behind everything enqueued so far.  Nothing is allocated, nothing waits for the device.  A refused descriptor
+// leaves the session as it was.
+void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_reaim_desc *cam = nullptr) {
+    if (cam && cam->struct_size != sizeof(f3d_session_reaim_desc))
+        fail(F3D_STATUS_VALUE, "f3d_session_reaim_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
+             "was built against another revision of f3d_terrain_pt.h", cam->struct_size, F3D_ABI_VERSION, sizeof(f3d_session_reaim_desc));
     if (r.struct_size != sizeof(f3d_session_rearm_desc))
         fail(F3D_STATUS_VALUE, "f3d_session_rearm_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
              "was built against another revision of f3d_terrain_pt.h", r.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_rearm_desc));
     if (s.peer[0].connected || s.peer[1].connected)
-        fail(F3D_STATUS_VALUE, "a session with peer halos cannot be re-armed: the frame counters its neighbours poll only rise");
+        fail(F3D_STATUS_VALUE, "a session with peer halos cannot be %s: the frame counters its neighbours poll only rise",
+             cam ? "re-aimed" : "re-armed");
+    const double t_host = now_s();
     f3d_terrain_ref_desc d = s.desc;
     d.sun_azimuth_deg = r.sun_azimuth_deg;
     d.sun_elevation_deg = r.sun_elevation_deg;
@@ -868,10 +875,19 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r) {
     d.observer_longitude_deg = r.observer_longitude_deg;
     d.pressure_mbar = r.pressure_mbar;
     d.temperature_c = r.temperature_c;
+    if (cam) {
+        for (int c = 0; c < 3; c++) {
+            d.cam_origin[c] = cam->cam_origin[c];
+            d.cam_look_at[c] = cam->cam_look_at[c];
+            d.cam_up[c] = cam->cam_up[c];
+        }
+        d.fov_y_deg = cam->fov_y_deg;
+    }
     validate_desc(d);
     FrameParams U{};
     const bool require_valid = fill_uniforms(d, U);
-    // (camera, DEM transform, spacing and spp are the create's: fill_uniforms gives them the same bits again)
+    // (DEM transform, spacing and spp are the create's, and without a re-aim the camera: fill_uniforms gives them the same
+    // bits again.  The AETHER post reads the camera from these uniforms at resolve time: its record holds no camera term.)
     FrameParams &P = s.params;
     P.cam = U.cam;
     P.light = U.light;
@@ -895,12 +911,14 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r) {
     P.tile_cost = nullptr;
     RearmParams R{};
     R.frame = P;
+    R.gbuffer_n = s.gbuffer_n;
     R.depth = s.depth;
     R.res[0] = s.res[0];
     R.res[1] = s.res[1];
     R.tile_cost = s.tile_cost;
     R.tiles = s.tile_cost ? frame_tile_count(P, nullptr) : 0u;
-    hip_check(launch_rearm(R, s.stream), "re-arm kernel");
+    if (cam) hip_check(launch_reaim(R, s.stream), "re-aim kernel");
+    else hip_check(launch_rearm(R, s.stream), "re-arm kernel");
     // host-side frame state as a new session has it
     s.cost_frame = s.order_frame = -1;
     s.rendered = false;
@@ -910,6 +928,7 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r) {
         b.last = -1;
         b.unjoined = false;
     }
+    s.reaim_seconds = cam ? now_s() - t_host : 0.0;
 }
 
 // The accumulation loop of a whole-image session up to the readback (render_terrain.rs:1123-1404): windows of frames
@@ -1284,13 +1303,22 @@ int f3d_session_rearm(f3d_session *s, const f3d_session_rearm_desc *desc, char *
     });
 }
 
+int f3d_session_reaim(f3d_session *s, const f3d_session_reaim_desc *desc, char *err, size_t errlen) {
+    return c_abi(err, errlen, [&] {
+        DeviceGuard g(checked(s).device);
+        if (!desc) fail(F3D_STATUS_VALUE, "null re-aim descriptor");
+        rearm(*s, desc->arm, desc);
+    });
+}
+
 int f3d_session_render(f3d_session *s, f3d_terrain_ref_out *out, char *err, size_t errlen) {
     return c_abi(err, errlen, [&] {
         DeviceGuard g(checked(s).device);
         if (!out) fail(F3D_STATUS_VALUE, "null output record");
         const double t_setup = now_s();
         hip_check(hipStreamSynchronize(s->stream), "setup sync");  // (the G-buffer or re-arm pass still in flight)
-        out->setup_seconds = now_s() - t_setup;
+        out->setup_seconds = now_s() - t_setup + s->reaim_seconds;
+        s->reaim_seconds = 0.0;
         render_loop(*s, out);
     });
 }

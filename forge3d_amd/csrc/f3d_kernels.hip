@@ -191,6 +191,11 @@ hipError_t launch_rearm(const RearmParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(k_rearm, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);
     return hipGetLastError();
 }
+hipError_t launch_reaim(const RearmParams &p, hipStream_t stream) {
+    if (frame_grid(p.frame) == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_reaim, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);
+    return hipGetLastError();
+}
 hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(k_resolve, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);
     return hipGetLastError();

@@ -29,15 +29,6 @@ struct ResolveParams {
     const float *depth;  // frame-0 depth AOV (the aerial-perspective post's segment length)
 };
 
-// Re-arm of a live session (f3d_session_rearm, k_rearm): frame = the new uniforms over the whole strip
-struct RearmParams {
-    FrameParams frame;        // gbuffer_n, accum_mean, welford_m2, head, stats, fix_count, sun_clear as the session has them
-    const float *depth;       // frame-0 depth AOV of the G-buffer pass
-    PackedReservoir *res[2];  // both ping-pong buffers, (rows + 2 * kHaloRows) x width each
-    uint32_t *tile_cost;      // wave durations of the longest-first dispatch (null: none)
-    uint32_t tiles;           // entries of tile_cost
-};
-
 hipError_t launch_head(const FrameParams &p, hipStream_t stream);  // sample-lane form: before launch_frame
 hipError_t launch_frame(const FrameParams &p, int variant, hipStream_t stream);
 hipError_t launch_trace(const FrameParams &p, uint32_t frames, hipStream_t stream);  // frames in flight: a batch of frames
@@ -49,6 +40,7 @@ uint32_t frame_tile_count(const FrameParams &p, uint32_t *grid);
 hipError_t launch_tile_order(const FrameParams &p, const uint32_t *cost, uint32_t *order, hipStream_t stream);
 hipError_t launch_gbuffer(const FrameParams &p, float4 *gbuffer_n, float *depth, hipStream_t stream);
 hipError_t launch_rearm(const RearmParams &p, hipStream_t stream);  // same grid and pixel mapping as launch_gbuffer
+hipError_t launch_reaim(const RearmParams &p, hipStream_t stream);  // ... and its LDS: the G-buffer pass and the re-arm in one
 hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream);
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream);
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream);

@@ -234,4 +234,15 @@ struct FrameParams {
     WfQueues wf;          // wavefront form of the trace batch (sun_o == null: k_trace traces the rays itself)
 };
 
+// Re-arm / re-aim of a live session (f3d_session_rearm, f3d_session_reaim; k_rearm, k_reaim): frame = the new uniforms
+// over the whole strip
+struct RearmParams {
+    FrameParams frame;        // gbuffer_n, accum_mean, welford_m2, head, stats, fix_count, sun_clear as the session has them
+    float4 *gbuffer_n;        // re-aim only: frame.gbuffer_n again, to be written under the new camera
+    float *depth;             // frame-0 depth AOV of the G-buffer pass (re-arm reads it, re-aim writes it)
+    PackedReservoir *res[2];  // both ping-pong buffers, (rows + 2 * kHaloRows) x width each
+    uint32_t *tile_cost;      // wave durations of the longest-first dispatch (null: none)
+    uint32_t tiles;           // entries of tile_cost
+};
+
 }  // namespace f3d

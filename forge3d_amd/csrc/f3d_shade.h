@@ -1007,9 +1007,10 @@ F3D_HD float2 sun_certificate(const FrameParams &P, uint32_t kind, V3 p, V3 n, f
     return c;
 }
 
+// (returns the G-buffer record it stored)
 template <class Pending>
-F3D_HD void gbuffer_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, float4 *gbuffer_n, float *depth,
-                          Pending &pend) {
+F3D_HD float4 gbuffer_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, float4 *gbuffer_n, float *depth,
+                            Pending &pend) {
     const size_t lp = (size_t)(gy - P.row_begin) * P.cam.width + gx;
     const V3 rd = camera_dir(P.cam, gx, gy, 0.0f, 0.0f);
     if (P.primary_start) {
@@ -1018,13 +1019,15 @@ F3D_HD void gbuffer_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, float4
     }
     const SurfaceHit hit = closest_hit(P, P.cam.origin, 1e-3f, rd, 1e30f, pend);
     if (P.sun_clear) P.sun_clear[lp] = sun_certificate(P, hit.kind, hit.p, hit.n, hit.t);
+    float4 g = float4{0.0f, 0.0f, 1.0f, 0.0f};
+    float t = f_from_bits(0x7fc00000u);
     if (hit.kind != 0u) {
-        gbuffer_n[lp] = float4{hit.n.x, hit.n.y, hit.n.z, (float)hit.kind};
-        depth[lp] = hit.t;
-    } else {
-        gbuffer_n[lp] = float4{0.0f, 0.0f, 1.0f, 0.0f};
-        depth[lp] = f_from_bits(0x7fc00000u);
+        g = float4{hit.n.x, hit.n.y, hit.n.z, (float)hit.kind};
+        t = hit.t;
     }
+    gbuffer_n[lp] = g;
+    depth[lp] = t;
+    return g;
 }
 
 // ---- re-arm of a live session (f3d_session_rearm): the sun certificate of a new sun without tracing the camera ray ----
@@ -1043,6 +1046,51 @@ F3D_HD void rearm_certificate(const FrameParams &P, uint32_t gx, uint32_t gy, co
         p = along(P.cam.origin, t, camera_dir(P.cam, gx, gy, 0.0f, 0.0f));
     }
     P.sun_clear[lp] = sun_certificate(P, kind, p, n, t);
+}
+
+// ---- the per-render state of a live session as a new session's create leaves it before its first frame (k_rearm, k_reaim) --
+// first sun-direction prediction of a pixel from its G-buffer record (k_trace_init, and a re-arm / re-aim)
+F3D_HD uint2 first_head(const FrameParams &P, float4 g) {
+    return uint2{0u, (g.w != 0.0f && dot(V3{g.x, g.y, g.z}, P.light.wi) > 0.0f) ? kHeadPrevValid : 0u};
+}
+// Accumulation, Welford M2, both reservoir buffers with their halo rows (buffer row r is cleared by the lane of owned row
+// r mod rows), tile costs, stats, retrace counters: one lane per owned pixel.  Uniform and coalesced (an 8x8 tile writes
+// 8-pixel row segments).
+F3D_HD void rearm_clear(const RearmParams &R, uint32_t gx, uint32_t gy) {
+    static_assert(sizeof(PackedReservoir) == sizeof(float4), "one 16-byte store clears a reservoir");
+    const FrameParams &P = R.frame;
+    const uint32_t W = P.cam.width, row = gy - P.row_begin, rows = P.row_end - P.row_begin;
+    const size_t lp = (size_t)row * W + gx;
+    const float4 zero4 = float4{0.0f, 0.0f, 0.0f, 0.0f};
+    P.accum_mean[lp] = zero4;
+    P.welford_m2[lp] = 0.0f;
+    for (uint32_t r = row; r < rows + 2u * kHaloRows; r += rows) {
+        const size_t i = (size_t)r * W + gx;
+        reinterpret_cast<float4 *>(R.res[0])[i] = zero4;  // (a packed reservoir is one 16-byte record)
+        reinterpret_cast<float4 *>(R.res[1])[i] = zero4;
+    }
+    if (R.tile_cost && lp < R.tiles) R.tile_cost[lp] = 0u;
+    if (lp == 0u) {
+        for (uint32_t k = 0u; k < 4u; k++) {
+            if (P.stats) P.stats[k] = 0u;
+            if (P.fix_count) P.fix_count[k] = 0u;
+        }
+    }
+}
+// the head record of a pixel whose G-buffer record is g (frames in flight: the first prediction, as k_trace_init)
+F3D_HD void rearm_head(const FrameParams &P, uint32_t gx, uint32_t gy, float4 g) {
+    if (P.head) P.head[(size_t)(gy - P.row_begin) * P.cam.width + gx] = P.trace ? first_head(P, g) : uint2{0u, 0u};
+}
+
+// ---- re-aim of a live session (f3d_session_reaim): a re-arm under a new camera.  The clears first (their stores are in
+// flight while the lane marches), then the G-buffer pass's own pixel under the new uniforms -- primary-ray certificate,
+// centre hit, sun certificate (once), normal and depth --, then the head record from the G-buffer record just made (this
+// lane's own pixel: no other lane's data, no barrier).
+template <class Pending>
+F3D_HD void reaim_pixel(const RearmParams &R, uint32_t gx, uint32_t gy, Pending &pend) {
+    rearm_clear(R, gx, gy);
+    const float4 g = gbuffer_pixel(R.frame, gx, gy, R.gbuffer_n, R.depth, pend);
+    rearm_head(R.frame, gx, gy, g);
 }
 
 // ---- final resolve: last spatial pass + validity (render_terrain.rs:1313-1337),

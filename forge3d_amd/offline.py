@@ -69,16 +69,20 @@ class OfflineTerrainViewer:
             self._camera = {**self._camera, "fov_y": self._fov}
 
     # -- output -----------------------------------------------------------------------
-    def render(self, width: Optional[int] = None, height: Optional[int] = None) -> dict:
+    def _call(self, width: Optional[int] = None, height: Optional[int] = None):
+        """The current scene as a call of the path tracer: (dem, width, height, camera, keywords)."""
         if self._dem is None:
             raise RuntimeError("no terrain loaded: call load_terrain() first")
         if self._camera is None:
             span = (self._dem.shape[1] - 1) * self._spacing[0]
             self.set_orbit_camera(28.0, 49.0, 1.25 * span)
-        self.last_result = hybrid_render_terrain_reference(
-            self._dem, int(width or self.width), int(height or self.height), dict(self._camera, fov_y=self._fov),
-            spacing=self._spacing, exaggeration=self._z_scale, sun_azimuth_deg=self._sun[0],
-            sun_elevation_deg=self._sun[1], **{k: v for k, v in self._render.items() if v is not None})
+        keywords = dict(spacing=self._spacing, exaggeration=self._z_scale, sun_azimuth_deg=self._sun[0],
+                        sun_elevation_deg=self._sun[1], **{k: v for k, v in self._render.items() if v is not None})
+        return self._dem, int(width or self.width), int(height or self.height), dict(self._camera, fov_y=self._fov), keywords
+
+    def render(self, width: Optional[int] = None, height: Optional[int] = None) -> dict:
+        dem, w, h, camera, keywords = self._call(width, height)
+        self.last_result = hybrid_render_terrain_reference(dem, w, h, camera, **keywords)
         return self.last_result
 
     def snapshot(self, path: Union[str, Path], width: Optional[int] = None, height: Optional[int] = None) -> None:

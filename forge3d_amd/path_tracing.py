@@ -229,24 +229,50 @@ def render_terrain_sequence(heightmap: "np.ndarray", width: int, height: int, ca
     refraction).  Every frame is checked by the wrapper's own rules before any device work; then ONE session renders the
     whole sequence, re-armed between frames (f3d_session_rearm: no new tables, allocations or G-buffer pass).
     """
+    yield from _render_sequence("render_terrain_sequence", heightmap, width, height, camera, frames, common, False)
+
+
+def render_terrain_camera_sequence(heightmap: "np.ndarray", width: int, height: int, *,
+                                   frames: "Sequence[Mapping[str, Any]]", **common):
+    """Generator: item i equals ``hybrid_render_terrain_reference(heightmap, width, height, frames[i]["camera"], **common,
+    **rest_of_frames[i])`` -- an orbit or a fly-over of one DEM.
+
+    ``frames[i]`` must hold ``"camera"`` (a camera dict, read as the one-shot call reads it: missing keys take the
+    wrapper's defaults) and may hold any of SEQUENCE_FRAME_KEYS.  Every frame is checked by the wrapper's own rules
+    before any device work; then ONE session renders the whole sequence, re-aimed between frames (f3d_session_reaim: no
+    new tables, allocations, streams or clears -- one pass traces the centre rays of the new view).
+    """
+    yield from _render_sequence("render_terrain_camera_sequence", heightmap, width, height, None, frames, common, True)
+
+
+def _render_sequence(name, heightmap, width, height, camera, frames, common, camera_per_frame: bool):
+    """The two sequence generators: one session, re-armed (camera_per_frame: re-aimed) between frames."""
     import inspect
 
     from .session import TerrainSession
 
     signature = inspect.signature(hybrid_render_terrain_reference)
-    defaults = {name: p.default for name, p in signature.parameters.items() if p.kind is inspect.Parameter.KEYWORD_ONLY}
-    for name in common:
-        if name not in defaults:
-            raise TypeError(f"render_terrain_sequence() got an unexpected keyword argument {name!r}")
+    defaults = {key: p.default for key, p in signature.parameters.items() if p.kind is inspect.Parameter.KEYWORD_ONLY}
+    for key in common:
+        if key not in defaults:
+            raise TypeError(f"{name}() got an unexpected keyword argument {key!r}")
     frames = [dict(f) for f in frames]
+    cameras = []
     for i, frame in enumerate(frames):
+        if camera_per_frame:
+            if "camera" not in frame:
+                raise ValueError(f"frames[{i}] lacks 'camera': every frame of {name} names its camera (a sequence under "
+                                 "one camera is render_terrain_sequence's)")
+            cameras.append(frame.pop("camera"))
+        else:
+            cameras.append(camera)
         for key in frame:
             if key not in SEQUENCE_FRAME_KEYS:
                 raise ValueError(f"frames[{i}] sets {key!r}, which a live session cannot change (per-frame keys: "
                                  f"{', '.join(SEQUENCE_FRAME_KEYS)}); render it with hybrid_render_terrain_reference")
     if getattr(_NATIVE, "hybrid_render_terrain_reference", None) is None:
         raise RuntimeError("hybrid_render_terrain_reference requires the native forge3d module with GPU support")
-    calls = [_prepare(heightmap, width, height, camera, {**defaults, **common, **frame}) for frame in frames]
+    calls = [_prepare(heightmap, width, height, cam, {**defaults, **common, **frame}) for cam, frame in zip(cameras, frames)]
     if not calls:
         return
     request, _, first = calls[0]
@@ -257,9 +283,13 @@ def render_terrain_sequence(heightmap: "np.ndarray", width: int, height: int, ca
     session = TerrainSession(request.dem, request.width, request.height, request.camera,
                              frames_in_flight=_NATIVE_MODULE.FRAMES_IN_FLIGHT_AUTO, **native)
     try:
-        for i, (_, sun, keywords) in enumerate(calls):
+        for i, (request, sun, keywords) in enumerate(calls):
             if i:
-                session.rearm(**{key: keywords[key] for key in TerrainSession.REARMABLE if key in keywords})
+                values = {key: keywords[key] for key in TerrainSession.REARMABLE if key in keywords}
+                if camera_per_frame:
+                    session.reaim(request.camera, **values)
+                else:
+                    session.rearm(**values)
             yield _with_sun(session.render(), sun)
     finally:
         session.close()

@@ -105,9 +105,36 @@ class TerrainSession:
         session stream, behind everything enqueued so far; a refused value leaves the session as it was."""
         given = dict(locals())
         given.pop("self")
+        r = self._rearm_desc(given)
+        self._check(self._lib.f3d_session_rearm(self._handle, C.byref(r), self._err, len(self._err)))
+        self._note_armed(r)
+
+    def reaim(self, camera=None, **rearmable):
+        """rearm() under a new camera: what ``TerrainSession(..., camera=camera, **values)`` renders, on this session.
+        ``camera`` is read exactly as the constructor reads it (a missing ``origin`` / ``look_at`` / ``up`` / ``fov_y`` /
+        ``exposure`` takes the wrapper's default, not the session's current value; an ``exposure=`` keyword wins over the
+        dict's); the other values as rearm() takes them (not given: kept).  One pass traces the centre rays again and
+        clears the per-render state; same contract as rearm().  Without a camera this is rearm()."""
+        if camera is None:
+            return self.rearm(**rearmable)
+        unknown = [k for k in rearmable if k not in self.REARMABLE]
+        if unknown:
+            raise TypeError(f"reaim() got an unexpected keyword argument {unknown[0]!r}")
+        a = _native.ReaimDesc()
+        a.struct_size = C.sizeof(_native.ReaimDesc)
+        a.cam_origin, a.cam_look_at, a.cam_up, a.fov_y_deg, exposure = _native.camera_members(dict(camera))
+        given = {k: rearmable.get(k) for k in self.REARMABLE}
+        if given["exposure"] is None:
+            given["exposure"] = exposure
+        a.arm = self._rearm_desc(given)
+        self._check(self._lib.f3d_session_reaim(self._handle, C.byref(a), self._err, len(self._err)))
+        self._note_armed(a.arm)
+
+    def _rearm_desc(self, given: dict) -> "_native.RearmDesc":
+        """f3d_session_rearm_desc of the re-armable values given (None: the session's current one)."""
         values = {k: (self._armed[k] if v is None else v) for k, v in given.items()}
-        if sun_color is not None:
-            values["sun_color"] = tuple(_native._extract_sun_color(sun_color))
+        if given["sun_color"] is not None:
+            values["sun_color"] = tuple(_native._extract_sun_color(given["sun_color"]))
         for key in ("seed", "max_frames", "min_frames"):
             if int(values[key]) < 0:
                 raise OverflowError("can't convert negative int to unsigned")
@@ -118,7 +145,9 @@ class TerrainSession:
             setattr(r, key, float(values[key]))
         r.sun_color = _native._f3(values["sun_color"])
         r.seed, r.max_frames, r.min_frames = int(values["seed"]), int(values["max_frames"]), int(values["min_frames"])
-        self._check(self._lib.f3d_session_rearm(self._handle, C.byref(r), self._err, len(self._err)))
+        return r
+
+    def _note_armed(self, r) -> None:
         # (as the library holds them: float32)
         self._armed = {k: (tuple(float(c) for c in r.sun_color) if k == "sun_color" else type(self._armed[k])(getattr(r, k)))
                        for k in self._armed}

@@ -89,22 +89,33 @@ class ViewerHandle(OfflineTerrainViewer):
         self._revision += 1
 
     # -- output -------------------------------------------------------------------------------------------
-    def render(self, width: Optional[int] = None, height: Optional[int] = None) -> dict:
+    def _call(self, width: Optional[int] = None, height: Optional[int] = None):
         if not self._open:
             raise ViewerError("viewer is closed")
         self._render.update(env_map=self._env, env_intensity=self._env_intensity, sun_intensity=self._sun_intensity)
-        return super().render(width, height)
+        return super()._call(width, height)
 
     def render_animation(self, animation: Sequence[Mapping[str, Any]], output_dir: Union[str, Path], fps: int = 30,
                          width: Optional[int] = None, height: Optional[int] = None, progress_callback=None) -> None:
         """A sequence of camera keyframes ({"phi_deg", "theta_deg", "radius"[, "fov_deg", "target"]} per frame),
         one PNG per frame named frame_0000.png ... like the reference's exporter (viewer.py:1270-1334); the DEM's
-        acceleration tables are built once (the library's scene cache)."""
+        acceleration tables are built once (the library's scene cache) and ONE session renders every frame, re-aimed per
+        key (path_tracing.render_terrain_camera_sequence): each PNG is what ``snapshot()`` under that key writes."""
+        from .path_tracing import render_terrain_camera_sequence
+
         out = Path(output_dir)
         out.mkdir(parents=True, exist_ok=True)
-        for i, key in enumerate(animation):
+        frames, call = [], None
+        for key in animation:
             self.set_orbit_camera(key["phi_deg"], key["theta_deg"], key["radius"], key.get("fov_deg"), key.get("target"))
-            self.snapshot(out / f"frame_{i:04d}.png", width, height)
+            call = self._call(width, height)
+            frames.append({"camera": call[3]})
+        if call is None:
+            return
+        dem, w, h, _, keywords = call
+        for i, result in enumerate(render_terrain_camera_sequence(dem, w, h, frames=frames, **keywords)):
+            self.last_result = result
+            _io.numpy_to_png(out / f"frame_{i:04d}.png", result["rgba"])
             if progress_callback:
                 progress_callback(i, len(animation))
 

@@ -337,6 +337,28 @@ int f3d_session_rearm(f3d_session *session, const f3d_session_rearm_desc *desc, 
 int f3d_session_render(f3d_session *session, f3d_terrain_ref_out *out, char *err, size_t errlen);
 /* Diagnostics (synchronises): content hashes of the sun-ray (out[0]) and primary-ray (out[1]) certificates. */
 int f3d_session_certificates(f3d_session *session, uint64_t out[2]);
+/* ---- re-aim: a re-arm under a new camera ------------------------------------------------------------------------
+ * What a new camera changes on top of a re-arm, still without a new session: the camera uniforms (all of them, the
+ * pixel cone included), and everything the create's G-buffer pass writes -- normals and hit kind, depth, primary-ray
+ * certificates (f3d_session_primary_start keeps returning the same pointer: its contents are the new view's after the
+ * pass), sun-ray certificates.  One pass (k_reaim) traces the centre rays again, computes each sun certificate once and
+ * clears the per-render state as the re-arm pass does; the longest-first tile order restarts from image order.  The
+ * AETHER post reads the camera height and the pixel rays from the uniforms at resolve time, so it follows.  DEM,
+ * exaggeration, spacing, mesh, environment map, image size, strip rows and spp stay the session's.  The next frames
+ * render exactly what a new session created with this camera and these values renders.  No ABI version bump: detected by
+ * the symbol f3d_session_reaim. */
+typedef struct f3d_session_reaim_desc {
+    uint32_t struct_size; /* = sizeof(f3d_session_reaim_desc) of the caller's header */
+    float cam_origin[3], cam_look_at[3], cam_up[3];
+    float fov_y_deg;
+    f3d_session_rearm_desc arm; /* everything a re-arm takes, same meaning (its struct_size is checked as well) */
+} f3d_session_reaim_desc;
+/* Same contract as f3d_session_rearm: validated by the create's code with its messages (a degenerate camera is refused
+ * with the create's text and status; the session stays unchanged and usable), asynchronous on the session stream behind
+ * everything enqueued so far, allocates nothing, works on the owned rows of a strip session, refused (status 1) for a
+ * session with connected peer halos.  The setup_seconds of the f3d_session_render that follows is the host time of this
+ * call plus that render's wait for the pass; it is not reported as zero. */
+int f3d_session_reaim(f3d_session *session, const f3d_session_reaim_desc *desc, char *err, size_t errlen);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);

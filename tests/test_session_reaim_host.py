@@ -1,0 +1,283 @@
+"""Re-aim of a live terrain session (f3d_session_reaim: a re-arm under a new camera), the parts that need no GPU.
+
+* The re-aim pass's pixel body (f3d_shade.h reaim_pixel, run per pixel by k_reaim) over a strip's state made under camera A
+  and sun A, with every per-render array filled with a byte pattern, leaves bit for bit what the G-buffer pass writes in a
+  fresh scene under camera B and sun B -- G-buffer, depth, primary-ray and sun-ray certificates -- and cleared arrays as a
+  create leaves them: 252 random scenes drawn like the re-arm harness draws them (DEM shapes, spacings, curvature on / off,
+  meshes walked binary and four wide, whole images and row strips, sessions with and without frames in flight and head
+  records), with camera pairs that include B = A, only fov_y changed, only up changed, B looking at sky only, B below the
+  terrain and B nadir over a lattice corner.  Through the product's headers compiled for the host (tests/reaim_host).
+* render_terrain_camera_sequence refuses what the wrapper refuses, with its exception types and messages, and what a live
+  session cannot change, before the device is touched; render_terrain_sequence still refuses a per-frame camera.
+* The header, the ctypes table and the descriptor's layout.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import re
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import scenes
+from test_session_rearm_host import _desc, _no_device, _wrapper_error
+
+ROOT = Path(__file__).resolve().parent.parent
+HARNESS = ROOT / "tests" / "reaim_host" / "reaim_harness.cpp"
+SCENES = 252
+KINDS = ("other", "same", "fov", "up", "sky", "below", "nadir")
+
+
+@pytest.fixture(scope="module")
+def harness():
+    out = Path(tempfile.mkdtemp(prefix="f3d_reaim_host_")) / "libreaim_host.so"
+    # (the emulator's flags, tests/emul/emul.py)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
+                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
+    lib = C.CDLL(str(out))
+    lib.reaim_check.restype = C.c_int
+    lib.reaim_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32,
+                                C.POINTER(C.c_uint64)]
+    return lib
+
+
+def _camera_b(kind, dem, cam, kw, rng):
+    """Camera B of a pair whose camera A is `cam`."""
+    h, w = dem.shape
+    sx, sz = kw["spacing"]
+    span = sx * max(h, w)
+    relief = kw["exaggeration"] * float(dem.max())
+    top = max(relief, 1.0)
+    if kw.get("mesh_vertices") is not None:
+        top = max(top, float(np.asarray(kw["mesh_vertices"])[:, 1].max()))
+    if kind == "same":
+        return dict(cam)
+    if kind == "fov":
+        return dict(cam, fov_y=float(cam["fov_y"] * rng.uniform(0.4, 0.9)))
+    if kind == "up":
+        return dict(cam, up=(float(rng.uniform(0.2, 0.6)), 1.0, float(rng.uniform(-0.5, 0.5))))
+    if kind == "sky":  # above everything, looking up: every pixel misses
+        o = (float(rng.uniform(-0.2, 0.2) * span), float(3.0 * top + 0.1 * span), float(rng.uniform(-0.2, 0.2) * span))
+        return {"origin": o, "look_at": (o[0] + 0.05 * span, o[1] + span, o[2]), "up": (0.0, 0.0, 1.0),
+                "fov_y": float(rng.uniform(20, 60)), "exposure": cam["exposure"]}
+    if kind == "below":  # under the datum, looking up at the underside
+        return {"origin": (float(rng.uniform(-0.3, 0.3) * span), float(-0.5 * top - 0.05 * span), float(rng.uniform(-0.3, 0.3) * span)),
+                "look_at": (0.0, float(0.5 * relief), 0.0), "up": (0.0, 1.0, 0.0), "fov_y": float(rng.uniform(30, 80)),
+                "exposure": cam["exposure"]}
+    if kind == "nadir":  # straight down over a lattice corner (f3d_setup.h: the DEM is centred on the origin)
+        i, j = int(rng.integers(1, w - 1)), int(rng.integers(1, h - 1))
+        x, z = np.float32(-0.5 * (w - 1.0) * sx) + np.float32(i * sx), np.float32(-0.5 * (h - 1.0) * sz) + np.float32(j * sz)
+        return {"origin": (float(x), float(2.0 * top + 0.3 * span), float(z)), "look_at": (float(x), 0.0, float(z)),
+                "up": (0.0, 0.0, -1.0), "fov_y": float(rng.uniform(20, 70)), "exposure": cam["exposure"]}
+    ang, dist = rng.uniform(0, 2 * np.pi), rng.uniform(0.2, 1.4) * span
+    return {"origin": (float(np.cos(ang) * dist), float(top * rng.uniform(0.3, 2.5)), float(np.sin(ang) * dist)),
+            "look_at": (float(rng.uniform(-0.2, 0.2) * span), float(relief * rng.uniform(0.0, 0.6)), float(rng.uniform(-0.2, 0.2) * span)),
+            "up": (0.0, 1.0, 0.0), "fov_y": float(rng.uniform(25, 80)), "exposure": float(rng.uniform(0.5, 2.0))}
+
+
+def _scene_pair(i):
+    """Scene i under (camera A, sun A) and (camera B, sun B): everything else equal but what a re-aim may change."""
+    dem, size, cam, kw = scenes.random_scene(9100 + i)
+    rng = np.random.default_rng(91_000 + i)
+    if i % 2 == 0 and "mesh_vertices" not in kw:  # half the scenes carry a mesh
+        span = kw["spacing"][0] * max(dem.shape)
+        relief = kw["exaggeration"] * float(dem.max())
+        kw["mesh_vertices"], kw["mesh_indices"] = scenes.box_city(n_boxes=int(rng.integers(1, 16)), seed=i, span=0.8 * span,
+                                                                  base=0.0, top=max(relief, 1.0))
+    if i % 3 == 0:  # strong curvature: a small sphere
+        kw.update(earth_model="sphere", refraction_model="none", sphere_radius_m=float(kw["spacing"][0] * max(dem.shape) * 3.0))
+    elif i % 3 == 1:
+        kw.update(earth_model="flat", refraction_model="none")  # curvature off
+    kind = KINDS[i % len(KINDS)]
+    cam_b = _camera_b(kind, dem, cam, kw, rng)
+    elevation = [90.0, -5.0, float(rng.uniform(1, 89)), float(rng.uniform(-20, 0)), float(rng.uniform(30, 89.9))][i % 5]
+    b = dict(kw, sun_azimuth_deg=float(rng.uniform(0, 360)), sun_elevation_deg=elevation, seed=int(rng.integers(0, 2 ** 31)),
+             sun_intensity=float(rng.uniform(0.0, 4.0)), observer_latitude_deg=float(rng.uniform(-80, 80)),
+             pressure_mbar=float(rng.uniform(700, 1050)), temperature_c=float(rng.uniform(-20, 35)))
+    if i % 4 == 3:
+        b = dict(kw)  # the camera alone
+    return dem, size, cam, kw, cam_b, b, kind
+
+
+def _check(harness, i, dem, size, cam, a, cam_b, b):
+    da, ka = _desc(dem, size, cam, a)
+    db, kb = _desc(dem, size, cam_b, b)
+    out = (C.c_uint64 * 11)()
+    form = 1 + (i // 2) % 2
+    rows = (0, 0) if i % 4 != 1 else (size[1] // 3, max(size[1] // 3 + 1, (2 * size[1]) // 3))  # a row strip
+    heads, trace = [(1, 1), (1, 0), (0, 0)][i % 3]
+    pattern = (0xA5, 0xFF, 0x7F, 0x01)[(i // 3) % 4]
+    rc = harness.reaim_check(C.addressof(da), C.addressof(db), form, rows[0], rows[1], trace, heads, pattern, out)
+    assert rc == 0, f"scene {i} refused"
+    del ka, kb
+    return dict(zip(("pixels", "hits", "gbuffer", "depth", "sun", "start", "uncleared", "heads", "sky_depth", "moved", "heads_set"),
+                    (int(v) for v in out)))
+
+
+def test_reaimed_state_equals_the_gbuffer_pass_under_the_new_camera(harness):
+    seen = {k: 0 for k in KINDS}
+    totals = {}
+    meshes = 0
+    for i in range(SCENES):
+        dem, size, cam, a, cam_b, b, kind = _scene_pair(i)
+        r = _check(harness, i, dem, size, cam, a, cam_b, b)
+        what = f"scene {i} ({kind}, {r['pixels']} pixels)"
+        assert r["gbuffer"] == 0, f"{what}: {r['gbuffer']} G-buffer records differ from the G-buffer pass's under camera B"
+        assert r["depth"] == 0, f"{what}: {r['depth']} depth words differ"
+        assert r["sky_depth"] == 0, f"{what}: {r['sky_depth']} sky pixels without the quiet NaN 0x7fc00000"
+        assert r["sun"] == 0, f"{what}: {r['sun']} sun-ray certificates differ"
+        assert r["start"] == 0, f"{what}: {r['start']} primary-ray certificates differ"
+        assert r["uncleared"] == 0, f"{what}: {r['uncleared']} bytes of per-render state were not cleared"
+        assert r["heads"] == 0, f"{what}: {r['heads']} head records differ from a create's"
+        if kind == "sky":
+            assert r["hits"] == 0, f"{what}: the sky-only camera sees {r['hits']} surface pixels"
+        if kind == "same":
+            assert r["moved"] == 0, what
+        seen[kind] += 1
+        meshes += a.get("mesh_vertices") is not None
+        for k, v in r.items():
+            totals[(kind, k)] = totals.get((kind, k), 0) + v
+    assert all(n >= SCENES // len(KINDS) for n in seen.values()), seen
+    assert meshes >= SCENES // 3
+    # the scenes say something: the views hit terrain, the new cameras move the G-buffer, predictions are made
+    for kind in ("other", "fov", "up", "below", "nadir"):
+        assert totals[(kind, "moved")] > totals[(kind, "pixels")] // 10, kind
+    for kind in ("other", "same", "fov", "up", "nadir"):
+        assert totals[(kind, "hits")] > totals[(kind, "pixels")] // 5, kind
+    assert sum(totals[(kind, "heads_set")] for kind in KINDS) > 0
+
+
+def test_the_harness_sees_a_stale_view(harness):
+    """The comparison can fail: without the re-aim, the state of camera A is not camera B's (the `moved` count is A's G-buffer
+    against B's), while the same pair through the re-aim agrees to the last bit."""
+    dem, size, cam, a, cam_b, b, kind = _scene_pair(0)
+    assert kind == "other"
+    r = _check(harness, 0, dem, size, cam, a, cam_b, b)
+    assert r["moved"] > r["pixels"] // 4 and r["gbuffer"] == r["depth"] == r["sun"] == r["start"] == 0
+
+
+# ---- render_terrain_camera_sequence: what it refuses, before any device work ---------------------------------------------
+CAM_B = {"origin": (40.0, 30.0, 80.0), "look_at": (0.0, 5.0, 0.0), "up": (0.0, 1.0, 0.0), "fov_y": 50.0}
+
+
+@pytest.mark.parametrize("key,value", [("spp", 4), ("width", 64), ("exaggeration", 2.0), ("mesh_vertices", np.zeros((3, 3))),
+                                       ("spacing", (2.0, 2.0)), ("env_map", None), ("atmosphere", None), ("exposure", 2.0)])
+def test_camera_sequence_refuses_a_key_a_live_session_cannot_change(monkeypatch, key, value):
+    from forge3d_amd.path_tracing import render_terrain_camera_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    frames = [{"camera": scenes.CAM}, {"camera": CAM_B, "sun_azimuth_deg": 20.0, key: value}]
+    with pytest.raises(ValueError, match=re.escape(f"frames[1] sets {key!r}")):
+        list(render_terrain_camera_sequence(dem, 32, 24, frames=frames, **scenes.scene_kwargs(dem)))
+
+
+def test_camera_sequence_refuses_a_frame_without_a_camera(monkeypatch):
+    from forge3d_amd.path_tracing import render_terrain_camera_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    frames = [{"camera": scenes.CAM}, {"camera": CAM_B}, {"sun_azimuth_deg": 20.0}]
+    with pytest.raises(ValueError, match=re.escape("frames[2] lacks 'camera'")):
+        list(render_terrain_camera_sequence(dem, 32, 24, frames=frames, **scenes.scene_kwargs(dem)))
+    with pytest.raises(TypeError, match="unexpected keyword argument 'bogus'"):
+        list(render_terrain_camera_sequence(dem, 32, 24, frames=[{"camera": CAM_B}], bogus=1, **scenes.scene_kwargs(dem)))
+    with pytest.raises(TypeError):  # the camera is per frame: there is no positional one
+        list(render_terrain_camera_sequence(dem, 32, 24, scenes.CAM, frames=[{"camera": CAM_B}], **scenes.scene_kwargs(dem)))
+
+
+def test_sequence_still_refuses_a_camera_per_frame(monkeypatch):
+    from forge3d_amd.path_tracing import render_terrain_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    with pytest.raises(ValueError, match=re.escape("frames[1] sets 'camera'")):
+        list(render_terrain_sequence(dem, 32, 24, scenes.CAM, frames=[{}, {"camera": CAM_B}], **scenes.scene_kwargs(dem)))
+
+
+def test_camera_sequence_refuses_what_the_wrapper_refuses_with_its_types_and_messages(monkeypatch):
+    """Every frame goes through the wrapper's own checks with ITS camera before the device is touched.  (The wrapper's camera
+    rule is that the camera is a mapping; a degenerate geometry -- origin == look_at -- is refused by the library's
+    validate_desc, for the one-shot and for the re-aim alike: tests/test_gpu_reaim.py.)"""
+    from forge3d_amd import path_tracing
+    from forge3d_amd.path_tracing import hybrid_render_terrain_reference, render_terrain_camera_sequence
+
+    _no_device(monkeypatch)
+    monkeypatch.setattr(path_tracing._NATIVE, "hybrid_render_terrain_reference", lambda *a, **k: (_ for _ in ()).throw(AssertionError("rendered")))
+    dem = scenes.golden_dem(8)
+    kw = scenes.scene_kwargs(dem)
+    kw.pop("sun_azimuth_deg"), kw.pop("sun_elevation_deg")
+    when = {"datetime_utc": "2024-06-21T12:00:00Z", "latitude_deg": 46.85, "longitude_deg": -121.76}
+    good = {"camera": scenes.CAM, "sun_azimuth_deg": 1.0}
+    cases = [
+        ({}, [good, {"camera": 5}]),                                                        # a camera that is no mapping
+        ({}, [good, {"camera": "origin"}]),
+        ({}, [good, {"camera": [("origin", (0, 1, 2)), 7]}]),
+        ({}, [{"camera": CAM_B, "solar_time": when, "sun_azimuth_deg": 10.0}]),            # solar_time + manual angles
+        ({"observer_latitude_deg": 12.0}, [{"camera": CAM_B, "solar_time": when}]),         # ... + a manual observer
+        ({}, [good, {"camera": CAM_B, "sun_color": (1.0, -1.0, 0.5)}]),                     # a bad colour in frame 1
+        ({}, [good, {"camera": CAM_B, "min_frames": 600, "max_frames": 512}]),              # budget order
+        ({"spp": 65}, [good]),
+    ]
+    for common, frames in cases:
+        for frame in frames:
+            rest = {k: v for k, v in frame.items() if k != "camera"}
+            want = _wrapper_error(lambda: hybrid_render_terrain_reference(dem, 32, 24, frame["camera"], **{**kw, **common, **rest}))
+            if want is not None:
+                break
+        assert want is not None, (common, frames)
+        with pytest.raises(want[0]) as got:
+            list(render_terrain_camera_sequence(dem, 32, 24, frames=frames, **kw, **common))
+        assert str(got.value) == want[1]
+    # a camera the wrapper accepts and the library refuses gets as far as the native layer in both forms
+    flat = {"camera": {"origin": (1.0, 2.0, 3.0), "look_at": (1.0, 2.0, 3.0)}}
+    assert _wrapper_error(lambda: hybrid_render_terrain_reference(dem, 32, 24, flat["camera"], sun_azimuth_deg=1.0, **kw)) is None
+    with pytest.raises(AssertionError, match="the device was touched"):
+        list(render_terrain_camera_sequence(dem, 32, 24, frames=[flat], sun_azimuth_deg=1.0, **kw))
+
+
+def test_reaim_reads_the_camera_as_the_constructor_does():
+    """TerrainSession.reaim and make_desc read the camera dict through one helper: missing keys take the wrapper's defaults."""
+    from forge3d_amd import _native
+
+    dem, size, _, kw = scenes.random_scene(9100)
+    for cam in ({}, {"origin": (1.0, 2.0, 3.0)}, {"fov_y": 30.0, "exposure": 2.5}, dict(scenes.CAM)):
+        d, keep = _desc(dem, size, cam, kw)
+        origin, look_at, up, fov, exposure = _native.camera_members(cam)
+        assert (list(d.cam_origin), list(d.cam_look_at), list(d.cam_up), d.fov_y_deg, d.exposure) == \
+               (list(origin), list(look_at), list(up), np.float32(fov), np.float32(exposure))
+        del keep
+    assert [list(v) if hasattr(v, "__len__") else v for v in _native.camera_members({})] == \
+           [[0.0, 50.0, 120.0], [0.0, 0.0, 0.0], [0.0, 1.0, 0.0], 45.0, 1.0]
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------
+def test_header_and_ctypes_table_declare_the_reaim_entry_point():
+    from forge3d_amd import _native
+
+    header = (ROOT / "include" / "f3d_terrain_pt.h").read_text()
+    assert re.search(r"\bf3d_session_reaim\s*\(", header)
+    assert "f3d_session_reaim" in {n for n, _, _ in _native.ABI}
+    assert "#define F3D_ABI_VERSION 6u" in header and _native.ABI_VERSION == 6  # additive: detected by the symbol
+    body = re.search(r"typedef struct f3d_session_reaim_desc \{(.*?)\} f3d_session_reaim_desc;", header, re.S).group(1)
+    assert body.split(";")[0].split() == ["uint32_t", "struct_size"]
+    fields = ("cam_origin", "cam_look_at", "cam_up", "fov_y_deg", "arm")
+    R = _native.ReaimDesc
+    assert [n for n, _ in R._fields_] == ["struct_size", *fields]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "f3d_terrain_pt.h"\nint main(void) { printf("%zu %zu ' + \
+          " ".join(["%zu"] * len(fields)) + '\\n", sizeof(f3d_session_reaim_desc), sizeof(f3d_session_rearm_desc), ' + \
+          ", ".join(f"offsetof(f3d_session_reaim_desc, {f})" for f in fields) + "); return 0; }\n"
+    with tempfile.TemporaryDirectory() as tmp:
+        c = Path(tmp) / "layout.c"
+        c.write_text(src)
+        exe = Path(tmp) / "layout"
+        subprocess.run(["gcc", "-I", str(ROOT / "include"), str(c), "-o", str(exe)], check=True)
+        got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [C.sizeof(R), C.sizeof(_native.RearmDesc), *(getattr(R, f).offset for f in fields)]
+    out = subprocess.run(["nm", "-D", "--defined-only", str(_native.library_path())], capture_output=True, text=True, check=True)
+    assert any(line.split()[-1] == "f3d_session_reaim" and " T " in line for line in out.stdout.splitlines())
+    text = (ROOT / "INTEGRATION.md").read_text()
+    assert "pub struct F3dSessionReaimDesc" in text and "f3d_session_reaim" in text
