@@ -22,6 +22,7 @@
 
 #include <unistd.h>
 
+#include "f3d_bvh_refit.h"
 #include "f3d_devmem.h"
 #include "f3d_launch.h"
 #include "f3d_lbvh.h"
@@ -88,6 +89,21 @@ struct f3d_session {
     FrameParams params{};
     std::shared_ptr<CachedTables> scene;  // shared, immutable acceleration tables (scene cache)
     std::shared_ptr<CachedMesh> mesh;     // shared, immutable device copy of the mesh and its BVH (mesh cache)
+    // re-mesh (f3d_session_remesh): what of mem.device_bytes stands for the shared mesh entry, the builder a new topology is
+    // built with, and -- from the first refit on -- the session's own vertices, leaf-order triangles and nodes with the
+    // refit's tables (parent links, arrival counters, two sets of scene bounds); the indices stay the entry's
+    uint64_t mesh_counted = 0;
+    uint32_t mesh_builder = 0;
+    bool mesh_grid = false;  // (F3D_MESH_FUSED builds: the occlusion rays march a grid made from the create's mesh)
+    struct OwnMesh {
+        float4 *vertices = nullptr, *tris = nullptr;
+        void *nodes = nullptr;
+        uint32_t *parent = nullptr, *counter = nullptr;
+        int *bounds = nullptr;
+        size_t vertex_bytes = 0, tri_bytes = 0, node_bytes = 0, table_bytes = 0;
+        uint32_t refits = 0;
+        bool live = false;
+    } own_mesh;
     TerrainTables tables;
     uint32_t width = 0, height = 0, row_begin = 0, row_end = 0, rows = 0;
     PackedReservoir *res[2] = {nullptr, nullptr};
@@ -382,7 +398,9 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
         if (builder < 1u || builder > 3u)
             fail(F3D_STATUS_VALUE, "mesh_builder must be 0 (automatic), 1 (host SAH, walked 4 wide), 2 (GPU LBVH) or 3 (host SAH, binary walk), got %u", builder);
         s.mesh = acquire_mesh(s.device, d.mesh_vertices, d.mesh_vertex_count, d.mesh_indices, d.mesh_index_count, builder, s.stream);
-        s.mem.device_bytes += s.mesh->mem.device_bytes;  // shared, but part of this render's working set
+        s.mesh_builder = builder;
+        s.mesh_counted = s.mesh->mem.device_bytes;
+        s.mem.device_bytes += s.mesh_counted;  // shared, but part of this render's working set
         P.mesh = s.mesh->dev;
 #if defined(F3D_MESH_FUSED)  // A/B build (f3d_shade.h occluded: measured slower, not in the shipped library)
         // ... and as a second band of the terrain's pyramid for the occlusion rays' march (f3d_meshgrid.h; F3D_MESH_GRID=0: the tree
@@ -396,6 +414,7 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
                 P.terrain.mesh_cell_tris = grid->tris;
                 P.terrain.mesh_top = grid->top;
                 s.mem.device_bytes += grid->bytes;
+                s.mesh_grid = true;
             }
         }
 #endif
@@ -849,7 +868,9 @@ void resolve(f3d_session &s, uint32_t frames, uint8_t *d_rgba, float *d_albedo, 
 // create's own code (validate_desc, fill_uniforms), then k_rearm -- or, for a new camera, k_reaim -- on the session
 // stream behind everything enqueued so far.  Nothing is allocated, nothing waits for the device.  A refused descriptor
 // leaves the session as it was.
-void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_reaim_desc *cam = nullptr) {
+// (rearm_desc: the checks that need no scene and the descriptor with the new members; rearm_apply: uniforms, pass, host
+// state.  f3d_session_remesh puts its mesh step between the validation and rearm_apply.)
+f3d_terrain_ref_desc rearm_desc(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_reaim_desc *cam, const char *done) {
     if (cam && cam->struct_size != sizeof(f3d_session_reaim_desc))
         fail(F3D_STATUS_VALUE, "f3d_session_reaim_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
              "was built against another revision of f3d_terrain_pt.h", cam->struct_size, F3D_ABI_VERSION, sizeof(f3d_session_reaim_desc));
@@ -857,9 +878,7 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_re
         fail(F3D_STATUS_VALUE, "f3d_session_rearm_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
              "was built against another revision of f3d_terrain_pt.h", r.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_rearm_desc));
     if (s.peer[0].connected || s.peer[1].connected)
-        fail(F3D_STATUS_VALUE, "a session with peer halos cannot be %s: the frame counters its neighbours poll only rise",
-             cam ? "re-aimed" : "re-armed");
-    const double t_host = now_s();
+        fail(F3D_STATUS_VALUE, "a session with peer halos cannot be %s: the frame counters its neighbours poll only rise", done);
     f3d_terrain_ref_desc d = s.desc;
     d.sun_azimuth_deg = r.sun_azimuth_deg;
     d.sun_elevation_deg = r.sun_elevation_deg;
@@ -883,9 +902,11 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_re
         }
         d.fov_y_deg = cam->fov_y_deg;
     }
-    validate_desc(d);
-    FrameParams U{};
-    const bool require_valid = fill_uniforms(d, U);
+    return d;
+}
+
+// d: validated; U / require_valid: fill_uniforms(d, U)
+void rearm_apply(f3d_session &s, const f3d_terrain_ref_desc &d, const FrameParams &U, bool require_valid, bool cam, double t_host) {
     // (DEM transform, spacing and spp are the create's, and without a re-aim the camera: fill_uniforms gives them the same
     // bits again.  The AETHER post reads the camera from these uniforms at resolve time: its record holds no camera term.)
     FrameParams &P = s.params;
@@ -898,6 +919,8 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_re
     if (s.aether.enabled) aether_sun_terms(s.aether, d);
     s.require_valid_reservoirs = require_valid;
     s.desc = d;
+    s.desc.mesh_vertices = nullptr;  // (a re-mesh validated them through d: read during the call only)
+    s.desc.mesh_indices = nullptr;
 
     join_bands(s);  // (the session stream after every band launch so far: the clears follow the last frame's kernels)
     P.band_begin = s.row_begin;
@@ -929,6 +952,161 @@ void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_re
         b.unjoined = false;
     }
     s.reaim_seconds = cam ? now_s() - t_host : 0.0;
+}
+
+void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_reaim_desc *cam = nullptr) {
+    const double t_host = now_s();
+    const f3d_terrain_ref_desc d = rearm_desc(s, r, cam, cam ? "re-aimed" : "re-armed");
+    validate_desc(d);
+    FrameParams U{};
+    const bool require_valid = fill_uniforms(d, U);
+    rearm_apply(s, d, U, require_valid, cam != nullptr, t_host);
+}
+
+// ---- re-mesh: the mesh of a live session moved (refit) or replaced (the create's path), then a re-aim ------------------
+// Positions only: the session's own copy of vertices, leaf-order triangles and nodes (made at the first refit; the cache
+// entry other sessions share is never written), the vertex upload in stream order, then the refit passes of
+// f3d_bvh_refit.h -- all on the session stream behind everything enqueued so far, no wait for the device.
+void remesh_refit(f3d_session &s, const float *vertices, uint32_t vertex_count) {
+    FrameParams &P = s.params;
+    f3d_session::OwnMesh &O = s.own_mesh;
+    const CachedMesh &E = *s.mesh;
+    const bool first = !O.live;
+    const uint32_t nodes = E.dev.bvh4_nodes ? E.dev.bvh4_node_count : E.dev.bvh_node_count;
+    if (first) {
+        f3d_session::OwnMesh N;
+        N.vertex_bytes = E.vertex_bytes;
+        N.tri_bytes = E.tri_bytes;
+        N.node_bytes = E.node_bytes;
+        N.table_bytes = 2u * (size_t)std::max(nodes, 1u) * sizeof(uint32_t) + 12u * sizeof(int);
+        // the count drops the shared entry's bytes and adds the private ones (the indices stay the entry's)
+        const uint64_t planned = s.mem.device_bytes - s.mesh_counted + E.index_bytes + N.vertex_bytes + N.tri_bytes + N.node_bytes + N.table_bytes;
+        if (planned > s.budget)
+            fail(F3D_STATUS_RENDER,
+                 "re-mesh exceeds the memory budget: the session's own copy of the mesh and the refit tables bring the tracked total to "
+                 "%llu > limit %llu", (unsigned long long)planned, (unsigned long long)s.budget);
+        std::vector<std::pair<void *, size_t>> got;
+        auto take = [&](size_t bytes, const char *what) {
+            void *p = s.mem.alloc(bytes, what);
+            got.emplace_back(p, bytes);
+            return p;
+        };
+        try {
+            N.vertices = (float4 *)take(N.vertex_bytes, "re-mesh vertices");
+            if (N.tri_bytes) N.tris = (float4 *)take(N.tri_bytes, "re-mesh BVH triangles");
+            if (N.node_bytes) N.nodes = take(N.node_bytes, "re-mesh BVH nodes");
+            N.parent = (uint32_t *)take((size_t)std::max(nodes, 1u) * sizeof(uint32_t), "re-mesh parent links");
+            N.counter = (uint32_t *)take((size_t)std::max(nodes, 1u) * sizeof(uint32_t), "re-mesh arrival counters");
+            N.bounds = (int *)take(12u * sizeof(int), "re-mesh scene bounds");
+        } catch (...) {
+            for (auto &g : got) s.mem.free(g.first, g.second);
+            throw;
+        }
+        s.mem.device_bytes -= s.mesh_counted;
+        s.mesh_counted = E.index_bytes;
+        s.mem.device_bytes += s.mesh_counted;
+        join_bands(s);
+        // topology words and the triangles' index words from the shared entry; counters at zero; both bound sets empty
+        if (N.tris) hip_check(hipMemcpyAsync(N.tris, E.dev.bvh_tris, N.tri_bytes, hipMemcpyDeviceToDevice, s.stream), "re-mesh copy");
+        if (N.nodes)
+            hip_check(hipMemcpyAsync(N.nodes, E.dev.bvh4_nodes ? (const void *)E.dev.bvh4_nodes : (const void *)E.dev.bvh_nodes, N.node_bytes,
+                                     hipMemcpyDeviceToDevice, s.stream), "re-mesh copy");
+        hip_check(hipMemsetAsync(N.counter, 0, (size_t)std::max(nodes, 1u) * sizeof(uint32_t), s.stream), "re-mesh counters");
+        static const int kEmptyBounds[12] = {0x7F800000, 0x7F800000, 0x7F800000, (int)0x807FFFFF, (int)0x807FFFFF, (int)0x807FFFFF,
+                                             0x7F800000, 0x7F800000, 0x7F800000, (int)0x807FFFFF, (int)0x807FFFFF, (int)0x807FFFFF};
+        hip_check(hipMemcpyAsync(N.bounds, kEmptyBounds, sizeof(kEmptyBounds), hipMemcpyHostToDevice, s.stream), "re-mesh bounds");
+        N.live = true;
+        O = N;
+        P.mesh.vertices = O.vertices;
+        if (O.tris) P.mesh.bvh_tris = O.tris;
+        if (O.nodes && E.dev.bvh4_nodes) P.mesh.bvh4_nodes = (const Bvh4Node *)O.nodes;
+        else if (O.nodes) P.mesh.bvh_nodes = (const BvhNode *)O.nodes;
+    } else {
+        join_bands(s);
+    }
+    const std::vector<float> v4 = pad_rgb_to_rgba(vertices, vertex_count, 0.0f);
+    upload_staged(O.vertices, v4.data(), v4.size() * sizeof(float), s.stream, true);
+    RefitParams R{};
+    R.vertices = O.vertices;
+    R.indices = E.dev.indices;
+    R.tris = O.tris;
+    R.tri_count = O.tris ? E.index_count / 3u : 0u;
+    if (E.dev.bvh4_nodes) {
+        R.wide = (Bvh4Node *)O.nodes;
+        R.wide_count = nodes;
+    } else {
+        R.nodes = (BvhNode *)O.nodes;
+        R.node_count = nodes;
+    }
+    R.parent = O.parent;
+    R.counter = O.counter;
+    R.bounds = O.bounds + 6u * (O.refits & 1u);
+    R.bounds_next = O.bounds + 6u * ((O.refits & 1u) ^ 1u);
+    hip_check(launch_bvh_refit(R, first, s.stream), "BVH refit kernels");
+    O.refits++;
+}
+
+// Another mesh: the create's path with the session's builder (cache, host SAH or LBVH; may wait and allocate like a create).
+void remesh_replace(f3d_session &s, const f3d_terrain_ref_desc &d) {
+    FrameParams &P = s.params;
+    f3d_session::OwnMesh &O = s.own_mesh;
+    std::shared_ptr<CachedMesh> fresh = acquire_mesh(s.device, d.mesh_vertices, d.mesh_vertex_count, d.mesh_indices, d.mesh_index_count,
+                                                     s.mesh_builder, s.stream);
+    const uint64_t own = O.live ? (uint64_t)O.vertex_bytes + O.tri_bytes + O.node_bytes + O.table_bytes : 0u;
+    const uint64_t planned = s.mem.device_bytes - s.mesh_counted - own + fresh->mem.device_bytes;
+    if (planned > s.budget)
+        fail(F3D_STATUS_RENDER, "re-mesh exceeds the memory budget: the new mesh brings the tracked total to %llu > limit %llu",
+             (unsigned long long)planned, (unsigned long long)s.budget);
+    // the old mesh goes only after the work enqueued before this call has finished
+    join_bands(s);
+    hip_check(hipStreamSynchronize(s.stream), "re-mesh");
+    if (O.live) {
+        const uint32_t nodes = s.mesh->dev.bvh4_nodes ? s.mesh->dev.bvh4_node_count : s.mesh->dev.bvh_node_count;
+        const size_t table = (size_t)std::max(nodes, 1u) * sizeof(uint32_t);
+        s.mem.free(O.vertices, O.vertex_bytes);
+        if (O.tris) s.mem.free(O.tris, O.tri_bytes);
+        if (O.nodes) s.mem.free(O.nodes, O.node_bytes);
+        s.mem.free(O.parent, table);
+        s.mem.free(O.counter, table);
+        s.mem.free(O.bounds, 12u * sizeof(int));
+        O = f3d_session::OwnMesh{};
+    }
+    s.mem.device_bytes -= s.mesh_counted;
+    s.mesh = fresh;
+    s.mesh_counted = fresh->mem.device_bytes;
+    s.mem.device_bytes += s.mesh_counted;
+    P.mesh = fresh->dev;
+}
+
+void remesh(f3d_session &s, const f3d_session_remesh_desc &m) {
+    if (m.struct_size != sizeof(f3d_session_remesh_desc))
+        fail(F3D_STATUS_VALUE, "f3d_session_remesh_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
+             "was built against another revision of f3d_terrain_pt.h", m.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_remesh_desc));
+    const double t_host = now_s();
+    f3d_terrain_ref_desc d = rearm_desc(s, m.aim.arm, &m.aim, "re-meshed");
+    if (!s.mesh)
+        fail(F3D_STATUS_VALUE, "this session was created without a mesh: a re-mesh moves or replaces a session's mesh, it cannot give it one");
+    if (s.mesh_grid)
+        fail(F3D_STATUS_VALUE, "this session's occlusion rays march a mesh grid made from the create's mesh (F3D_MESH_FUSED build): it cannot be re-meshed");
+    if (m.mesh_indices) {  // another mesh: every mesh check of the create
+        d.mesh_vertices = m.mesh_vertices;
+        d.mesh_vertex_count = m.mesh_vertex_count;
+        d.mesh_indices = m.mesh_indices;
+        d.mesh_index_count = m.mesh_index_count;
+    } else {  // positions only: the create's vertex checks, with its texts and statuses (validate_desc, f3d_setup.h)
+        if (!m.mesh_vertices || m.mesh_vertex_count == 0) fail(F3D_STATUS_RENDER, "mesh vertices must be a non-empty flat [x,y,z] list");
+        if (m.mesh_vertex_count != s.params.mesh.vertex_count)
+            fail(F3D_STATUS_VALUE, "a re-mesh without mesh_indices moves the session's mesh: %u vertices given, its topology has %u (pass "
+                 "mesh_indices for another mesh)", m.mesh_vertex_count, s.params.mesh.vertex_count);
+        for (size_t i = 0; i < (size_t)m.mesh_vertex_count * 3; i++)
+            if (!std::isfinite(m.mesh_vertices[i])) fail(F3D_STATUS_RENDER, "mesh vertices contain non-finite values");
+    }
+    validate_desc(d);
+    FrameParams U{};
+    const bool require_valid = fill_uniforms(d, U);
+    if (m.mesh_indices) remesh_replace(s, d);
+    else remesh_refit(s, m.mesh_vertices, m.mesh_vertex_count);
+    rearm_apply(s, d, U, require_valid, true, t_host);
 }
 
 // The accumulation loop of a whole-image session up to the readback (render_terrain.rs:1123-1404): windows of frames
@@ -1308,6 +1486,14 @@ int f3d_session_reaim(f3d_session *s, const f3d_session_reaim_desc *desc, char *
         DeviceGuard g(checked(s).device);
         if (!desc) fail(F3D_STATUS_VALUE, "null re-aim descriptor");
         rearm(*s, desc->arm, desc);
+    });
+}
+
+int f3d_session_remesh(f3d_session *s, const f3d_session_remesh_desc *desc, char *err, size_t errlen) {
+    return c_abi(err, errlen, [&] {
+        DeviceGuard g(checked(s).device);
+        if (!desc) fail(F3D_STATUS_VALUE, "null re-mesh descriptor");
+        remesh(*s, *desc);
     });
 }
 

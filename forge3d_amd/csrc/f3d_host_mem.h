@@ -287,7 +287,10 @@ StagingPair &staging_for_current_device() {
     if (!slot) slot.reset(new StagingPair());
     return *slot;
 }
-void upload_staged(void *dst, const void *src, size_t bytes, hipStream_t stream) {
+// stream_ordered: also a small upload goes through the staging pair in stream order (a re-mesh writes vertices that
+// frames already enqueued on a non-blocking stream still read: a plain hipMemcpy is not ordered behind them), and the
+// call does not wait for the copies at its end (up to two chunks are on their way when it returns)
+void upload_staged(void *dst, const void *src, size_t bytes, hipStream_t stream, bool stream_ordered = false) {
     constexpr size_t kChunk = 4u << 20;
     StagingPair &pair = staging_for_current_device();
     std::lock_guard<std::mutex> lock(pair.mutex);
@@ -296,7 +299,7 @@ void upload_staged(void *dst, const void *src, size_t bytes, hipStream_t stream)
             hip_check(hipHostMalloc(&pair.buffer[i], kChunk, hipHostMallocPortable), "pinned staging buffer");
             hip_check(hipEventCreateWithFlags(&pair.drained[i], hipEventDisableTiming), "staging event");
         }
-    if (bytes < (256u << 10)) {  // small: one plain copy
+    if (bytes < (256u << 10) && !stream_ordered) {  // small: one plain copy
         hip_check(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "upload");
         return;
     }
@@ -309,6 +312,7 @@ void upload_staged(void *dst, const void *src, size_t bytes, hipStream_t stream)
         hip_check(hipEventRecord(pair.drained[turn], stream), "staging event");
         done += n;
     }
+    if (stream_ordered) return;  // (no wait for the device: whoever takes a staging buffer next waits for ITS event above)
     hip_check(hipEventSynchronize(pair.drained[0]), "upload");  // the staging pair is free again, the data is on its way in order
     hip_check(hipEventSynchronize(pair.drained[1]), "upload");
 }
@@ -370,6 +374,7 @@ struct CachedMesh {
     uint32_t vertex_count = 0, index_count = 0, builder = 0;
     Ledger mem;
     MeshDev dev{};
+    size_t vertex_bytes = 0, index_bytes = 0, tri_bytes = 0, node_bytes = 0;  // of dev's buffers (a re-mesh's private copy: f3d_session_remesh)
     uint64_t stamp = 0;
     // the mesh as a second band of a DEM's pyramid (f3d_meshgrid.h), per grid geometry; bands == nullptr: this mesh has none there
     struct Grid {
@@ -424,6 +429,8 @@ std::shared_ptr<CachedMesh> acquire_mesh(int device, const float *vertices, uint
     MeshDev &M = e->dev;
     M.vertices = dv;
     M.indices = di;
+    e->vertex_bytes = v4.size() * sizeof(float);
+    e->index_bytes = (size_t)index_count * sizeof(uint32_t);
     M.vertex_count = vertex_count;
     M.index_count = index_count;
     M.traversal_mode = 0u;
@@ -436,6 +443,8 @@ std::shared_ptr<CachedMesh> acquire_mesh(int device, const float *vertices, uint
             M.bvh_nodes = lb.nodes;
             M.bvh_tris = lb.tris;
             M.bvh_node_count = lb.node_count;
+            e->node_bytes = lb.node_bytes;
+            e->tri_bytes = lb.tri_bytes;
         }
         hip_check(hipStreamSynchronize(stream), "GPU LBVH build");  // other sessions may walk it from their streams
     } else {
@@ -448,6 +457,8 @@ std::shared_ptr<CachedMesh> acquire_mesh(int device, const float *vertices, uint
             float4 *dt = (float4 *)e->mem.alloc(bvh.tris.size() * sizeof(float), "mesh BVH triangles");
             hip_check(hipMemcpy(dt, bvh.tris.data(), bvh.tris.size() * sizeof(float), hipMemcpyHostToDevice), "BVH upload");
             M.bvh_tris = dt;
+            e->tri_bytes = bvh.tris.size() * sizeof(float);
+            e->node_bytes = wide.empty() ? bvh.nodes.size() * sizeof(BvhNode) : wide.size() * sizeof(Bvh4Node);
             if (!wide.empty()) {
                 Bvh4Node *dw = (Bvh4Node *)e->mem.alloc(wide.size() * sizeof(Bvh4Node), "mesh BVH nodes (4-wide)");
                 hip_check(hipMemcpy(dw, wide.data(), wide.size() * sizeof(Bvh4Node), hipMemcpyHostToDevice), "BVH upload");

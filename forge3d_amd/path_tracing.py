@@ -245,8 +245,26 @@ def render_terrain_camera_sequence(heightmap: "np.ndarray", width: int, height: 
     yield from _render_sequence("render_terrain_camera_sequence", heightmap, width, height, None, frames, common, True)
 
 
-def _render_sequence(name, heightmap, width, height, camera, frames, common, camera_per_frame: bool):
-    """The two sequence generators: one session, re-armed (camera_per_frame: re-aimed) between frames."""
+def render_terrain_mesh_sequence(heightmap: "np.ndarray", width: int, height: int, camera: "dict | None" = None, *,
+                                 frames: "Sequence[Mapping[str, Any]]", **common):
+    """Generator: item i equals ``hybrid_render_terrain_reference(heightmap, width, height, camera_i, **common,
+    **frames[i])`` -- geometry moving on one DEM (a vehicle, turbine blades, buildings growing).
+
+    ``common`` must hold a mesh (``mesh_vertices`` and ``mesh_indices``).  ``frames[i]`` may hold ``"mesh_vertices"``
+    (on the indices of ``common``: the session's BVH is refitted on the GPU), optionally ``"mesh_indices"`` (another
+    mesh: built as a new session builds it), optionally ``"camera"`` (camera_i; without it the positional ``camera``) and
+    any of SEQUENCE_FRAME_KEYS; a key a frame does not name is ``common``'s, as in the one-shot call.  Every frame is
+    checked by the wrapper's own rules before any device work; then ONE session renders the whole sequence, re-meshed
+    between frames (f3d_session_remesh) wherever the mesh changes.
+    """
+    if common.get("mesh_vertices") is None or common.get("mesh_indices") is None:
+        raise ValueError("render_terrain_mesh_sequence needs the mesh in the common keywords (mesh_vertices and mesh_indices): a "
+                         "live session cannot be given a mesh it was created without")
+    yield from _render_sequence("render_terrain_mesh_sequence", heightmap, width, height, camera, frames, common, False, True)
+
+
+def _render_sequence(name, heightmap, width, height, camera, frames, common, camera_per_frame: bool, mesh_per_frame: bool = False):
+    """The sequence generators: one session, re-armed (camera_per_frame: re-aimed; mesh_per_frame: re-meshed) between frames."""
     import inspect
 
     from .session import TerrainSession
@@ -264,9 +282,13 @@ def _render_sequence(name, heightmap, width, height, camera, frames, common, cam
                 raise ValueError(f"frames[{i}] lacks 'camera': every frame of {name} names its camera (a sequence under "
                                  "one camera is render_terrain_sequence's)")
             cameras.append(frame.pop("camera"))
+        elif mesh_per_frame and "camera" in frame:
+            cameras.append(frame.pop("camera"))
         else:
             cameras.append(camera)
         for key in frame:
+            if mesh_per_frame and key in ("mesh_vertices", "mesh_indices"):
+                continue
             if key not in SEQUENCE_FRAME_KEYS:
                 raise ValueError(f"frames[{i}] sets {key!r}, which a live session cannot change (per-frame keys: "
                                  f"{', '.join(SEQUENCE_FRAME_KEYS)}); render it with hybrid_render_terrain_reference")
@@ -282,11 +304,17 @@ def _render_sequence(name, heightmap, width, height, camera, frames, common, cam
     # one-shot calls size frames in flight automatically: so does the session (same byte counts in the result)
     session = TerrainSession(request.dem, request.width, request.height, request.camera,
                              frames_in_flight=_NATIVE_MODULE.FRAMES_IN_FLIGHT_AUTO, **native)
+    held = (first["mesh_vertices"], first["mesh_indices"])  # the mesh the session holds
     try:
         for i, (request, sun, keywords) in enumerate(calls):
             if i:
                 values = {key: keywords[key] for key in TerrainSession.REARMABLE if key in keywords}
-                if camera_per_frame:
+                mesh = (keywords["mesh_vertices"], keywords["mesh_indices"])
+                if mesh_per_frame and not (np.array_equal(mesh[0], held[0]) and np.array_equal(mesh[1], held[1])):
+                    # this frame's mesh (its own or common's) on the topology the session holds: a refit; else the create's path
+                    session.remesh(mesh[0], None if np.array_equal(mesh[1], held[1]) else mesh[1], request.camera, **values)
+                    held = mesh
+                elif mesh_per_frame or camera_per_frame:
                     session.reaim(request.camera, **values)
                 else:
                     session.rearm(**values)

@@ -64,6 +64,7 @@ class TerrainSession:
                        "observer_latitude_deg": float(desc.observer_latitude_deg),
                        "observer_longitude_deg": float(desc.observer_longitude_deg),
                        "pressure_mbar": float(desc.pressure_mbar), "temperature_c": float(desc.temperature_c)}
+        self._camera = dict(camera or {})  # what remesh() keeps when no camera is given
         self.row_begin = int(row_begin)
         self.row_end = int(row_end) or int(height)
         self.rows = self.row_end - self.row_begin
@@ -120,6 +121,46 @@ class TerrainSession:
         unknown = [k for k in rearmable if k not in self.REARMABLE]
         if unknown:
             raise TypeError(f"reaim() got an unexpected keyword argument {unknown[0]!r}")
+        a = self._reaim_desc(camera, rearmable)
+        self._check(self._lib.f3d_session_reaim(self._handle, C.byref(a), self._err, len(self._err)))
+        self._note_armed(a.arm)
+        self._camera = dict(camera)
+
+    def remesh(self, mesh_vertices, mesh_indices=None, camera=None, **rearmable):
+        """reaim() under a moved or another mesh: what ``TerrainSession(..., mesh_vertices=..., mesh_indices=..., camera=camera,
+        **values)`` renders, on this session.  Without ``mesh_indices`` the vertices (the session's count) move the
+        session's mesh: uploaded in stream order, the BVH refitted on the GPU -- no host build, no wait, nothing allocated
+        after the first call; the tree keeps its topology, so large motion costs walk time, never the image.  With
+        ``mesh_indices`` (the same ones for a fresh tree, or another mesh) the create's path runs.  ``camera`` None keeps the
+        current one (and the current exposure); otherwise it is read as reaim() reads it.  Same contract as reaim(): a
+        refused value leaves the session as it was, rendering the old mesh."""
+        unknown = [k for k in rearmable if k not in self.REARMABLE]
+        if unknown:
+            raise TypeError(f"remesh() got an unexpected keyword argument {unknown[0]!r}")
+        mv = np.ascontiguousarray(mesh_vertices, dtype=np.float32)
+        if mv.ndim != 2 or mv.shape[1] != 3:
+            raise ValueError("mesh_vertices must have shape (N, 3)")
+        m = _native.RemeshDesc()
+        m.struct_size = C.sizeof(_native.RemeshDesc)
+        m.mesh_vertices, m.mesh_vertex_count = mv.ctypes.data, mv.shape[0]
+        mi = None
+        if mesh_indices is not None:
+            mi = np.ascontiguousarray(mesh_indices, dtype=np.uint32)
+            if mi.ndim != 2 or mi.shape[1] != 3:
+                raise ValueError("mesh_indices must have shape (M, 3)")
+            m.mesh_indices, m.mesh_index_count = mi.ctypes.data, mi.size
+        if camera is None:
+            m.aim = self._reaim_desc(self._camera, dict(rearmable, exposure=rearmable.get("exposure", self._armed["exposure"])))
+        else:
+            m.aim = self._reaim_desc(camera, rearmable)
+        self._check(self._lib.f3d_session_remesh(self._handle, C.byref(m), self._err, len(self._err)))
+        del mv, mi
+        self._note_armed(m.aim.arm)
+        if camera is not None:
+            self._camera = dict(camera)
+
+    def _reaim_desc(self, camera, rearmable: dict) -> "_native.ReaimDesc":
+        """f3d_session_reaim_desc of a camera dict and the re-armable values given."""
         a = _native.ReaimDesc()
         a.struct_size = C.sizeof(_native.ReaimDesc)
         a.cam_origin, a.cam_look_at, a.cam_up, a.fov_y_deg, exposure = _native.camera_members(dict(camera))
@@ -127,8 +168,7 @@ class TerrainSession:
         if given["exposure"] is None:
             given["exposure"] = exposure
         a.arm = self._rearm_desc(given)
-        self._check(self._lib.f3d_session_reaim(self._handle, C.byref(a), self._err, len(self._err)))
-        self._note_armed(a.arm)
+        return a
 
     def _rearm_desc(self, given: dict) -> "_native.RearmDesc":
         """f3d_session_rearm_desc of the re-armable values given (None: the session's current one)."""

@@ -311,7 +311,7 @@ int f3d_session_setup_ms(f3d_session *session, double *out, uint32_t count);
  * per-pixel sun-ray certificates (recomputed from the resident G-buffer, the camera rays are not traced again), the
  * AETHER record's sun terms, and the per-render state (accumulation, Welford, both reservoir buffers with their halo
  * rows -- caller-owned ones included --, head records, tile costs, stats), cleared as a new session has them.  Camera,
- * DEM, exaggeration, spacing, mesh, environment map, image size, strip rows, spp, earth / refraction model and
+ * DEM, exaggeration, spacing, mesh (see f3d_session_remesh), environment map, image size, strip rows, spp, earth / refraction model and
  * atmosphere LUTs stay the session's; observer latitude / longitude, pressure and temperature are re-armable (they
  * only enter the curvature of the secondary rays).  The next frames render exactly what a new session created with
  * these values renders.  Added without an ABI version bump (no existing struct or signature changed): a binding
@@ -344,7 +344,7 @@ int f3d_session_certificates(f3d_session *session, uint64_t out[2]);
  * pass), sun-ray certificates.  One pass (k_reaim) traces the centre rays again, computes each sun certificate once and
  * clears the per-render state as the re-arm pass does; the longest-first tile order restarts from image order.  The
  * AETHER post reads the camera height and the pixel rays from the uniforms at resolve time, so it follows.  DEM,
- * exaggeration, spacing, mesh, environment map, image size, strip rows and spp stay the session's.  The next frames
+ * exaggeration, spacing, mesh (see f3d_session_remesh), environment map, image size, strip rows and spp stay the session's.  The next frames
  * render exactly what a new session created with this camera and these values renders.  No ABI version bump: detected by
  * the symbol f3d_session_reaim. */
 typedef struct f3d_session_reaim_desc {
@@ -359,6 +359,36 @@ typedef struct f3d_session_reaim_desc {
  * session with connected peer halos.  The setup_seconds of the f3d_session_render that follows is the host time of this
  * call plus that render's wait for the pass; it is not reported as zero. */
 int f3d_session_reaim(f3d_session *session, const f3d_session_reaim_desc *desc, char *err, size_t errlen);
+/* ---- re-mesh: a re-aim under a moved or another mesh -----------------------------------------------------------------
+ * What a new mesh changes on top of a re-aim, still without a new session: the geometry standing on the terrain, and
+ * with it everything the re-aim pass recomputes (centre hits, normals, depth, both certificates).  Two paths:
+ *   mesh_indices == NULL   positions only, the REFIT path: mesh_vertex_count must be the session's.  The vertices are
+ *     uploaded in stream order and the session's BVH is refitted on the GPU -- triangles gathered again in leaf order,
+ *     scene bounds and the build's padding recomputed on the device, leaf boxes, then inner boxes bottom-up; the tree's
+ *     topology stays, so large motion costs walk time, never the image.  Asynchronous on the session stream behind
+ *     everything enqueued so far, no wait for the device.  The FIRST refit gives the session its own vertices, leaf-order
+ *     triangles and nodes (the cached mesh other sessions share is never written; the indices stay shared) and the refit's
+ *     tables: only that call allocates, against memory_budget_bytes (too small: refused, status 2); gpu_resource_bytes
+ *     then exceeds a fresh session's by those tables and never grows again.
+ *   mesh_indices != NULL   another mesh (any counts), the create's path with the session's builder: mesh cache, host SAH
+ *     or LBVH build; may wait and allocate like a create; the old mesh is released once the work enqueued before the call
+ *     has finished; gpu_resource_bytes equals a fresh session's.  Also the way to a fresh tree when motion has degraded a
+ *     refitted one: pass the same indices again.
+ * Validated by the create's code with its messages and statuses (mesh checks included; a non-finite vertex: "mesh
+ * vertices contain non-finite values", status 2); a refusal leaves the session unchanged, usable and rendering the old
+ * mesh.  Refused with status 1: a session created without a mesh, a vertex count other than the session's without
+ * mesh_indices, connected peer halos, a session whose occlusion rays march a mesh grid (F3D_MESH_FUSED builds).  The
+ * next frames render exactly what a new session created with this mesh, this camera and these values renders.  No ABI
+ * version bump: detected by the symbol f3d_session_remesh. */
+typedef struct f3d_session_remesh_desc {
+    uint32_t struct_size;         /* = sizeof(f3d_session_remesh_desc) of the caller's header */
+    const float *mesh_vertices;   /* HOST, (mesh_vertex_count, 3), read during the call only */
+    uint32_t mesh_vertex_count;
+    const uint32_t *mesh_indices; /* NULL = the session's topology (positions only: the refit path); else another mesh */
+    uint32_t mesh_index_count;
+    f3d_session_reaim_desc aim;   /* camera + everything a re-arm takes, same meaning */
+} f3d_session_remesh_desc;
+int f3d_session_remesh(f3d_session *session, const f3d_session_remesh_desc *desc, char *err, size_t errlen);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);

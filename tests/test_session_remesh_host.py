@@ -1,0 +1,266 @@
+"""Re-mesh of a live terrain session (f3d_session_remesh: a re-aim under a moved or another mesh), the parts that need no GPU.
+
+* The refit passes' per-thread bodies (f3d_bvh_refit.h: what k_remesh_gather / k_remesh_link / k_remesh_refit_* run) on
+  the host, in a shuffled order, over trees the product's builders made -- the threaded binary tree, the same tree four
+  wide, and a binary tree in the GPU LBVH's output form -- for 216 random scenes (box_city, _blob_mesh and
+  random_scene_city_inside meshes) under six motions: identity, a rigid shift, per-vertex jitter, the vertex positions
+  permuted across the scene, every vertex collapsed to one point, the mesh moved 10^4 units away.  (i) Every leaf box holds
+  its triangles by the padding the build's rule gives for the NEW bounds, every parent holds its children, empty wide
+  slots keep (+inf, +inf), no topology word changes.  (ii) 2 000 rays aimed at the moved mesh's bounding box plus 500
+  random ones a scene: closest hit (hit, t, normal bit for bit) and any hit through the refitted tree equal mesh_sweep over
+  the moved mesh and the walk of a tree built fresh from it.  An any-hit walk stops at the first triangle it accepts in
+  visiting order, so its t and normal are not the sweep's by design (f3d_shade.h mesh_bvh<ANY>); its answer is compared.
+* render_terrain_mesh_sequence refuses what the wrapper refuses, with its types and texts, before the device is touched;
+  the two older generators still refuse a per-frame mesh.
+* The header, the ctypes table and the descriptor's layout.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import re
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import scenes
+from test_session_rearm_host import _no_device, _wrapper_error
+
+ROOT = Path(__file__).resolve().parent.parent
+HARNESS = ROOT / "tests" / "remesh_host" / "remesh_harness.cpp"
+SCENES = 216
+MOTIONS = ("identity", "shift", "jitter", "permuted", "collapsed", "away")
+SEEN = ("identity", "shift", "jitter", "permuted")  # motions after which the mesh must still be hit
+AIMED, RANDOM = 2000, 500
+FIELDS = ("leaf_boxes", "parent_boxes", "empty_slots", "topology", "triangles", "counters", "pad", "closest", "any", "fresh_closest",
+          "fresh_any", "aimed", "aimed_hits", "rays", "hits", "form", "nodes")
+
+
+@pytest.fixture(scope="module")
+def harness():
+    out = Path(tempfile.mkdtemp(prefix="f3d_remesh_host_")) / "libremesh_host.so"
+    # (the emulator's flags, tests/emul/emul.py)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
+                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
+    lib = C.CDLL(str(out))
+    lib.remesh_check.restype = C.c_int
+    lib.remesh_check.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
+                                 C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.remesh_stale.restype = C.c_int
+    lib.remesh_stale.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
+                                 C.POINTER(C.c_uint64)]
+    return lib
+
+
+def _mesh(i):
+    """Mesh of scene i: box_city, _blob_mesh or the mesh of random_scene_city_inside."""
+    rng = np.random.default_rng(31_000 + i)
+    kind = (i // 18) % 3
+    if kind == 0:
+        return scenes.box_city(n_boxes=int(rng.integers(1, 60)), seed=i, span=float(rng.uniform(20.0, 100.0)), top=float(rng.uniform(3.0, 40.0)))
+    if kind == 1:
+        v, t = scenes._blob_mesh(rng, n_lat=int(rng.integers(3, 12)), n_lon=int(rng.integers(3, 14)), radius=float(rng.uniform(0.3, 30.0)))
+        return v + rng.uniform(-20.0, 20.0, 3).astype(np.float32), t
+    for k in range(64):
+        kw = scenes.random_scene_city_inside(5000 + 64 * i + k)[3]
+        if kw.get("mesh_vertices") is not None:
+            return np.asarray(kw["mesh_vertices"], np.float32), np.asarray(kw["mesh_indices"], np.uint32)
+    raise AssertionError("no mesh drawn")
+
+
+def moved(v, motion, rng):
+    """The vertex positions after a motion (float32, same count)."""
+    v = np.asarray(v, np.float32)
+    extent = float(np.max(v.max(axis=0) - v.min(axis=0))) + 1e-3
+    if motion == "identity":
+        return v.copy()
+    if motion == "shift":
+        return (v + rng.uniform(-0.5, 0.5, 3).astype(np.float32) * np.float32(extent)).astype(np.float32)
+    if motion == "jitter":
+        return (v + rng.uniform(-0.08, 0.08, v.shape).astype(np.float32) * np.float32(extent)).astype(np.float32)
+    if motion == "permuted":
+        return v[rng.permutation(len(v))].copy()
+    if motion == "collapsed":
+        return np.tile(v[int(rng.integers(0, len(v)))], (len(v), 1)).astype(np.float32)
+    if motion == "away":
+        return (v + np.float32(1e4)).astype(np.float32)
+    raise ValueError(motion)
+
+
+def _check(harness, i, v, t, motion):
+    rng = np.random.default_rng(47_000 + i)
+    b = np.ascontiguousarray(moved(v, motion, rng))
+    a = np.ascontiguousarray(v, np.float32)
+    idx = np.ascontiguousarray(t, np.uint32)
+    out = (C.c_uint64 * 17)()
+    form, twice = 1 + (i // 6) % 3, (i // 3) % 2
+    rc = harness.remesh_check(a.ctypes.data, b.ctypes.data, len(a), idx.ctypes.data, idx.size, form, twice, AIMED, RANDOM, 1000 + i, out)
+    assert rc == 0, f"scene {i} refused"
+    return dict(zip(FIELDS, (int(x) for x in out))), form
+
+
+def test_refitted_trees_hold_the_moved_mesh_and_walk_like_the_sweep(harness):
+    seen = {m: 0 for m in MOTIONS}
+    forms = {1: 0, 2: 0, 3: 0}
+    aimed = {m: [0, 0] for m in MOTIONS}
+    for i in range(SCENES):
+        motion = MOTIONS[i % len(MOTIONS)]
+        v, t = _mesh(i)
+        r, form = _check(harness, i, v, t, motion)
+        what = f"scene {i} ({motion}, form {form} -> {r['form']}, {len(t)} triangles, {r['nodes']} nodes)"
+        assert r["rays"] >= 2000 and r["aimed"] == AIMED
+        assert r["leaf_boxes"] == 0, f"{what}: {r['leaf_boxes']} leaf boxes do not hold their triangles by the new pad"
+        assert r["parent_boxes"] == 0, f"{what}: {r['parent_boxes']} parent boxes do not hold a child"
+        assert r["empty_slots"] == 0, f"{what}: {r['empty_slots']} planes of empty wide slots are not +inf"
+        assert r["topology"] == 0, f"{what}: {r['topology']} topology words changed"
+        assert r["triangles"] == 0, f"{what}: {r['triangles']} leaf-order triangles are not the moved ones"
+        assert r["counters"] == 0, f"{what}: {r['counters']} arrival counters are not back at zero"
+        assert r["pad"] == 0, f"{what}: the refit's padding is not the build's for the new bounds"
+        assert r["closest"] == 0, f"{what}: {r['closest']} closest hits differ from the sweep over the moved mesh"
+        assert r["any"] == 0, f"{what}: {r['any']} any-hit answers differ from the sweep's"
+        assert r["fresh_closest"] == 0, f"{what}: {r['fresh_closest']} closest hits differ from a fresh tree's"
+        assert r["fresh_any"] == 0, f"{what}: {r['fresh_any']} any-hit answers differ from a fresh tree's"
+        seen[motion] += 1
+        forms[r["form"]] += 1
+        aimed[motion][0] += r["aimed"]
+        aimed[motion][1] += r["aimed_hits"]
+    assert all(n >= SCENES // len(MOTIONS) for n in seen.values()), seen
+    assert all(n >= SCENES // 6 for n in forms.values()), forms
+    shares = {m: hit / max(n, 1) for m, (n, hit) in aimed.items()}
+    print("share of aimed rays that hit, by motion:", {m: round(s, 3) for m, s in shares.items()})
+    for m in SEEN:  # the walks are compared on rays that meet triangles
+        assert shares[m] >= 0.20, shares
+
+
+def test_the_harness_sees_boxes_that_were_not_refitted(harness):
+    """The comparison can fail: triangles moved under boxes left where they were lose hits, in every form."""
+    v, t = scenes.box_city(n_boxes=40, seed=3, span=60.0)
+    b = np.ascontiguousarray((v + np.float32([9.0, 4.0, -7.0])).astype(np.float32))
+    a, idx = np.ascontiguousarray(v, np.float32), np.ascontiguousarray(t, np.uint32)
+    for form in (1, 2, 3):
+        out = (C.c_uint64 * 3)()
+        assert harness.remesh_stale(a.ctypes.data, b.ctypes.data, len(a), idx.ctypes.data, idx.size, form, 2000, 5, out) == 0
+        assert out[2] > 400 and out[0] > out[2] // 10 and out[1] > out[2] // 10, (form, list(out))
+
+
+# ---- render_terrain_mesh_sequence: what it refuses, before any device work ---------------------------------------------
+CAM_B = {"origin": (40.0, 30.0, 80.0), "look_at": (0.0, 5.0, 0.0), "up": (0.0, 1.0, 0.0), "fov_y": 50.0}
+
+
+def _city():
+    v, t = scenes.box_city(n_boxes=6, seed=5, span=40.0)
+    return v, t
+
+
+@pytest.mark.parametrize("key,value", [("spp", 4), ("width", 64), ("exaggeration", 2.0), ("spacing", (2.0, 2.0)), ("env_map", None),
+                                       ("atmosphere", None), ("exposure", 2.0)])
+def test_mesh_sequence_refuses_a_key_a_live_session_cannot_change(monkeypatch, key, value):
+    from forge3d_amd.path_tracing import render_terrain_mesh_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    v, t = _city()
+    frames = [{}, {"mesh_vertices": v + 1.0, "sun_azimuth_deg": 20.0, key: value}]
+    with pytest.raises(ValueError, match=re.escape(f"frames[1] sets {key!r}")):
+        list(render_terrain_mesh_sequence(dem, 32, 24, scenes.CAM, frames=frames, mesh_vertices=v, mesh_indices=t, **scenes.scene_kwargs(dem)))
+
+
+def test_mesh_sequence_needs_a_mesh_in_the_common_keywords(monkeypatch):
+    from forge3d_amd.path_tracing import render_terrain_mesh_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    v, t = _city()
+    kw = scenes.scene_kwargs(dem)
+    with pytest.raises(ValueError, match="needs the mesh in the common keywords"):
+        list(render_terrain_mesh_sequence(dem, 32, 24, scenes.CAM, frames=[{"mesh_vertices": v}], **kw))
+    with pytest.raises(ValueError, match="needs the mesh in the common keywords"):
+        list(render_terrain_mesh_sequence(dem, 32, 24, scenes.CAM, frames=[{"mesh_vertices": v, "mesh_indices": t}], **kw))
+    with pytest.raises(TypeError, match="unexpected keyword argument 'bogus'"):
+        list(render_terrain_mesh_sequence(dem, 32, 24, scenes.CAM, frames=[{}], bogus=1, mesh_vertices=v, mesh_indices=t, **kw))
+
+
+def test_the_other_sequences_still_refuse_a_mesh_per_frame(monkeypatch):
+    from forge3d_amd.path_tracing import render_terrain_camera_sequence, render_terrain_sequence
+
+    _no_device(monkeypatch)
+    dem = scenes.golden_dem(8)
+    v, t = _city()
+    kw = dict(scenes.scene_kwargs(dem), mesh_vertices=v, mesh_indices=t)
+    text = re.escape("frames[1] sets 'mesh_vertices', which a live session cannot change")
+    with pytest.raises(ValueError, match=text):
+        list(render_terrain_sequence(dem, 32, 24, scenes.CAM, frames=[{}, {"mesh_vertices": v + 1.0}], **kw))
+    with pytest.raises(ValueError, match=text):
+        list(render_terrain_camera_sequence(dem, 32, 24, frames=[{"camera": scenes.CAM}, {"camera": CAM_B, "mesh_vertices": v + 1.0}], **kw))
+
+
+def test_mesh_sequence_refuses_what_the_wrapper_refuses_with_its_types_and_messages(monkeypatch):
+    """Every frame goes through the wrapper's own checks -- with ITS mesh, camera and values -- before the device is touched."""
+    from forge3d_amd import path_tracing
+    from forge3d_amd.path_tracing import hybrid_render_terrain_reference, render_terrain_mesh_sequence
+
+    _no_device(monkeypatch)
+    monkeypatch.setattr(path_tracing._NATIVE, "hybrid_render_terrain_reference", lambda *a, **k: (_ for _ in ()).throw(AssertionError("rendered")))
+    dem = scenes.golden_dem(8)
+    v, t = _city()
+    kw = dict(scenes.scene_kwargs(dem), mesh_vertices=v, mesh_indices=t)
+    kw.pop("sun_azimuth_deg"), kw.pop("sun_elevation_deg")
+    when = {"datetime_utc": "2024-06-21T12:00:00Z", "latitude_deg": 46.85, "longitude_deg": -121.76}
+    good = {"sun_azimuth_deg": 1.0}
+    cases = [
+        ({}, [good, {"mesh_vertices": np.zeros((4, 2), np.float32)}]),                    # vertices that are not (N, 3)
+        ({}, [good, {"mesh_vertices": np.zeros(9, np.float32)}]),
+        ({}, [good, {"mesh_vertices": v, "mesh_indices": np.zeros((2, 4), np.uint32)}]),  # indices that are not (M, 3)
+        ({}, [good, {"mesh_vertices": v + 1.0, "camera": 5}]),                            # a camera that is no mapping
+        ({}, [{"mesh_vertices": v, "solar_time": when, "sun_azimuth_deg": 10.0}]),        # solar_time + manual angles
+        ({}, [good, {"mesh_vertices": v, "sun_color": (1.0, -1.0, 0.5)}]),                # a bad colour in frame 1
+        ({}, [good, {"mesh_vertices": v, "min_frames": 600, "max_frames": 512}]),         # budget order
+        ({"spp": 65}, [good]),
+    ]
+    for common, frames in cases:
+        for frame in frames:
+            rest = {k: val for k, val in frame.items() if k != "camera"}
+            want = _wrapper_error(lambda: hybrid_render_terrain_reference(dem, 32, 24, frame.get("camera", scenes.CAM), **{**kw, **common, **rest}))
+            if want is not None:
+                break
+        assert want is not None, (common, frames)
+        with pytest.raises(want[0]) as got:
+            list(render_terrain_mesh_sequence(dem, 32, 24, scenes.CAM, frames=frames, **kw, **common))
+        assert str(got.value) == want[1]
+    # frames the wrapper accepts get as far as the native layer
+    with pytest.raises(AssertionError, match="the device was touched"):
+        list(render_terrain_mesh_sequence(dem, 32, 24, scenes.CAM, frames=[good, {"mesh_vertices": v + 2.0, "camera": CAM_B}], **kw))
+
+
+# ---- the C ABI ------------------------------------------------------------------------------------------------------------
+def test_header_and_ctypes_table_declare_the_remesh_entry_point():
+    from forge3d_amd import _native
+
+    header = (ROOT / "include" / "f3d_terrain_pt.h").read_text()
+    assert re.search(r"\bf3d_session_remesh\s*\(", header)
+    assert "f3d_session_remesh" in {n for n, _, _ in _native.ABI}
+    assert "#define F3D_ABI_VERSION 6u" in header and _native.ABI_VERSION == 6  # additive: detected by the symbol
+    body = re.search(r"typedef struct f3d_session_remesh_desc \{(.*?)\} f3d_session_remesh_desc;", header, re.S).group(1)
+    assert body.split(";")[0].split() == ["uint32_t", "struct_size"]
+    fields = ("mesh_vertices", "mesh_vertex_count", "mesh_indices", "mesh_index_count", "aim")
+    R = _native.RemeshDesc
+    assert [n for n, _ in R._fields_] == ["struct_size", *fields]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "f3d_terrain_pt.h"\nint main(void) { printf("%zu %zu ' + \
+          " ".join(["%zu"] * len(fields)) + '\\n", sizeof(f3d_session_remesh_desc), sizeof(f3d_session_reaim_desc), ' + \
+          ", ".join(f"offsetof(f3d_session_remesh_desc, {f})" for f in fields) + "); return 0; }\n"
+    with tempfile.TemporaryDirectory() as tmp:
+        c = Path(tmp) / "layout.c"
+        c.write_text(src)
+        exe = Path(tmp) / "layout"
+        subprocess.run(["gcc", "-I", str(ROOT / "include"), str(c), "-o", str(exe)], check=True)
+        got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [C.sizeof(R), C.sizeof(_native.ReaimDesc), *(getattr(R, f).offset for f in fields)]
+    out = subprocess.run(["nm", "-D", "--defined-only", str(_native.library_path())], capture_output=True, text=True, check=True)
+    assert any(line.split()[-1] == "f3d_session_remesh" and " T " in line for line in out.stdout.splitlines())
+    text = (ROOT / "INTEGRATION.md").read_text()
+    assert "pub struct F3dSessionRemeshDesc" in text and "f3d_session_remesh" in text
+    for comment in ("mesh (see f3d_session_remesh), environment map, image size, strip rows, spp",
+                    "mesh (see f3d_session_remesh), environment map, image size, strip rows and spp stay"):
+        assert comment in header
