@@ -134,6 +134,18 @@ class RemeshDesc(C.Structure):
     ]
 
 
+class ReterrainDesc(C.Structure):
+    """f3d_session_reterrain_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("heights", C.c_void_p),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("x0", C.c_uint32), ("y0", C.c_uint32),
+        ("exaggeration", C.c_float),
+        ("aim", ReaimDesc),
+    ]
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -170,6 +182,7 @@ ABI = [
     ("f3d_session_render", C.c_int, [C.c_void_p, _P(Out), C.c_char_p, C.c_size_t]),
     ("f3d_session_reaim", C.c_int, [C.c_void_p, _P(ReaimDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_remesh", C.c_int, [C.c_void_p, _P(RemeshDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_reterrain", C.c_int, [C.c_void_p, _P(ReterrainDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
     ("f3d_session_halo", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p), _P(C.c_uint64)]),
@@ -237,7 +250,7 @@ KERNEL_FLAGS = [
     # Round 4 took the spills out at the source -- 160 -> 12 bytes of scratch per lane -- and with them the reason: the
     # default is now 1.1 % FASTER, 8 690 -> 8 785 Msamples/s in one call, same image; profiles/r04_variant_ab.log)
 ]
-HIP_SOURCES = ["f3d_kernels.hip", "f3d_host.hip", "f3d_denoise.hip", "f3d_smoke.hip", "f3d_smoke_sim.hip", "f3d_composite.hip", "f3d_lbvh.hip", "f3d_bvh_refit.hip", "f3d_wavefront.hip",
+HIP_SOURCES = ["f3d_kernels.hip", "f3d_host.hip", "f3d_denoise.hip", "f3d_smoke.hip", "f3d_smoke_sim.hip", "f3d_composite.hip", "f3d_lbvh.hip", "f3d_bvh_refit.hip", "f3d_retable.hip", "f3d_wavefront.hip",
                "f3d_aether_bake.hip", "f3d_aether_ref.hip"]
 
 

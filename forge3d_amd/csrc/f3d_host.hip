@@ -27,6 +27,7 @@
 #include "f3d_launch.h"
 #include "f3d_lbvh.h"
 #include "f3d_meshgrid.h"
+#include "f3d_retable.h"
 #include "f3d_setup.h"
 #include "f3d_tables.h"
 
@@ -104,6 +105,17 @@ struct f3d_session {
         uint32_t refits = 0;
         bool live = false;
     } own_mesh;
+    // re-terrain (f3d_session_reterrain): what of mem.device_bytes stands for the shared scene entry, and -- from the first
+    // re-terrain on -- the session's own leaf and band tables (TableLayout sizes; `tables` and params.terrain then name
+    // them, the entry other sessions share is never written) and the staging buffer of the largest block so far
+    uint64_t scene_counted = 0;
+    struct OwnTerrain {
+        LeafRec *leaves = nullptr;
+        NodeRec *bands = nullptr;
+        float *staging = nullptr;
+        size_t leaf_bytes = 0, band_bytes = 0, staging_bytes = 0;
+        bool live = false;  // the frames read the own tables
+    } own_terrain;
     TerrainTables tables;
     uint32_t width = 0, height = 0, row_begin = 0, row_end = 0, rows = 0;
     PackedReservoir *res[2] = {nullptr, nullptr};
@@ -336,7 +348,8 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
     g_setup_ms = nullptr;
     clock.last = std::chrono::steady_clock::now();  // (acquire_tables lapped its own phases)
     s.tables = s.scene->tables;
-    s.mem.device_bytes += s.scene->mem.device_bytes;  // shared, but part of this render's working set
+    s.scene_counted = s.scene->mem.device_bytes;
+    s.mem.device_bytes += s.scene_counted;  // shared, but part of this render's working set
     apply_layout(s.tables.layout, P.terrain);
     P.terrain.leaves = s.tables.leaves;
     P.terrain.nodes = s.tables.nodes;
@@ -363,6 +376,7 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
             hip_check(launch_horizon_build(P.terrain, hz.table, s.stream), "far-horizon table build");
             hip_check(hipStreamSynchronize(s.stream), "far-horizon table build");  // other sessions may use it from their streams
             s.mem.device_bytes += bytes;
+            s.scene_counted += bytes;
             s.scene->horizons.push_back(hz);
             have = &s.scene->horizons.back();
         }
@@ -1109,6 +1123,113 @@ void remesh(f3d_session &s, const f3d_session_remesh_desc &m) {
     rearm_apply(s, d, U, require_valid, true, t_host);
 }
 
+// ---- re-terrain: new DEM samples on a live session, its tables patched on the GPU, then a re-aim -------------------------
+// The block is uploaded in stream order into the session's staging buffer and the two passes of f3d_retable.h patch the
+// session's OWN leaf and band tables (taken at the first call and filled from the shared scene-cache entry by device
+// copies; that entry is never written and stays referenced -- the copies read it -- but is no longer counted).  All on the
+// session stream behind everything enqueued so far, no wait for the device; only the first call, and a call with a block
+// larger than any before (the staging buffer grows: the old one goes back through the allocator, which waits for the work
+// that reads it), allocate.  Every refusal comes before the first change of the session.
+void reterrain(f3d_session &s, const f3d_session_reterrain_desc &t) {
+    if (t.struct_size != sizeof(f3d_session_reterrain_desc))
+        fail(F3D_STATUS_VALUE, "f3d_session_reterrain_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
+             "was built against another revision of f3d_terrain_pt.h", t.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_reterrain_desc));
+    const double t_host = now_s();
+    f3d_terrain_ref_desc d = rearm_desc(s, t.aim.arm, &t.aim, "re-terrained");
+    if (s.mesh_grid)
+        fail(F3D_STATUS_VALUE, "this session's occlusion rays march a mesh grid binned on the create's terrain cells (F3D_MESH_FUSED build): it cannot be re-terrained");
+    if (s.params.terrain.horizon)
+        fail(F3D_STATUS_VALUE, "this session built the far-horizon table of its DEM (F3D_IBL_HORIZON=1): it cannot be re-terrained, the table would be stale");
+    const uint32_t w = s.desc.dem_width, h = s.desc.dem_height;
+    if (!t.heights || t.width == 0u || t.height == 0u)
+        fail(F3D_STATUS_VALUE, "re-terrain block is empty (%ux%u samples): a block holds at least one sample", t.width, t.height);
+    if (t.x0 >= w || t.y0 >= h || t.width > w - t.x0 || t.height > h - t.y0)
+        fail(F3D_STATUS_VALUE, "re-terrain block of %ux%u samples at sample (%u, %u) leaves the session's %ux%u DEM (another DEM size needs a new session)",
+             t.width, t.height, t.x0, t.y0, w, h);
+    const bool whole = t.x0 == 0u && t.y0 == 0u && t.width == w && t.height == h;
+    if (t.exaggeration != 0.0f && !(t.exaggeration == s.desc.exaggeration)) {
+        if (!whole)
+            fail(F3D_STATUS_VALUE, "a new exaggeration (%g, the session's is %g) rescales every sample: give it with the whole %ux%u DEM, not with a block",
+                 (double)t.exaggeration, (double)s.desc.exaggeration, w, h);
+        d.exaggeration = t.exaggeration;
+    }
+    validate_desc(d);
+    const size_t samples = (size_t)t.width * t.height, block_bytes = samples * sizeof(float);
+    {
+        uint32_t bad = 0u;  // (an exponent field of all ones: inf / NaN)
+        for (size_t i = 0; i < samples; i++) {
+            uint32_t v;
+            memcpy(&v, t.heights + i, sizeof v);
+            bad |= (uint32_t)((v & 0x7F800000u) == 0x7F800000u);
+        }
+        if (bad) fail(F3D_STATUS_UPLOAD, "terrain heightfield contains non-finite samples");
+    }
+    FrameParams U{};
+    const bool require_valid = fill_uniforms(d, U);
+
+    FrameParams &P = s.params;
+    f3d_session::OwnTerrain &O = s.own_terrain;
+    const TableLayout &L = s.tables.layout;
+    const size_t leaf_bytes = L.leaf_count * sizeof(LeafRec), band_bytes = L.band_count * sizeof(NodeRec);
+    const bool take_tables = !O.leaves, grow = block_bytes > O.staging_bytes;
+    if (take_tables || grow) {
+        // the count drops the shared entry's bytes and adds the own tables and the staging buffer
+        const uint64_t planned = s.mem.device_bytes - (take_tables ? s.scene_counted : 0u) + (take_tables ? leaf_bytes + band_bytes : 0u) -
+                                 (grow ? O.staging_bytes : 0u) + (grow ? block_bytes : 0u);
+        if (planned > s.budget)
+            fail(F3D_STATUS_RENDER,
+                 "re-terrain exceeds the memory budget: the session's own tables and the staging buffer of a %ux%u block bring the tracked total to "
+                 "%llu > limit %llu", t.width, t.height, (unsigned long long)planned, (unsigned long long)s.budget);
+        std::vector<std::pair<void *, size_t>> got;
+        auto take = [&](size_t bytes, const char *what) {
+            void *p = s.mem.alloc(bytes, what);
+            got.emplace_back(p, bytes);
+            return p;
+        };
+        f3d_session::OwnTerrain N = O;
+        try {
+            if (grow) N.staging = (float *)take(block_bytes, "re-terrain staging");
+            if (take_tables) {
+                N.leaves = (LeafRec *)take(leaf_bytes, "re-terrain leaf table");
+                N.bands = (NodeRec *)take(band_bytes, "re-terrain band tables");
+                N.leaf_bytes = leaf_bytes;
+                N.band_bytes = band_bytes;
+            }
+        } catch (...) {
+            for (auto &g : got) s.mem.free(g.first, g.second);
+            throw;
+        }
+        if (grow) {
+            if (O.staging) s.mem.free(O.staging, O.staging_bytes);
+            N.staging_bytes = block_bytes;
+        }
+        if (take_tables) {
+            s.mem.device_bytes -= s.scene_counted;
+            s.scene_counted = 0u;
+        }
+        O = N;
+    }
+    join_bands(s);
+    if (!O.live) {
+        hip_check(hipMemcpyAsync(O.leaves, s.tables.leaves, leaf_bytes, hipMemcpyDeviceToDevice, s.stream), "re-terrain copy");
+        hip_check(hipMemcpyAsync(O.bands, s.tables.bands, band_bytes, hipMemcpyDeviceToDevice, s.stream), "re-terrain copy");
+    }
+    upload_staged(O.staging, t.heights, block_bytes, s.stream, true);
+    hip_check(launch_retable(retable_params(L, O.staging, t.x0, t.y0, t.width, t.height, d.exaggeration, O.leaves, O.bands), s.stream),
+              "re-terrain table kernels");
+    if (!O.live) {
+        O.live = true;
+        s.tables.leaves = O.leaves;
+        s.tables.bands = O.bands;
+        s.tables.dev.leaves = O.leaves;
+        s.tables.dev.bands = O.bands;
+        P.terrain.leaves = O.leaves;
+        P.terrain.bands = O.bands;
+        P.terrain.mesh_bands = O.bands;  // (no mesh grid: refused above)
+    }
+    rearm_apply(s, d, U, require_valid, true, t_host);
+}
+
 // The accumulation loop of a whole-image session up to the readback (render_terrain.rs:1123-1404): windows of frames
 // until converged or capped, the final resolve (and AETHER post), the copies into the caller's buffers.  Everything of
 // f3d_terrain_ref_out but setup_seconds.
@@ -1494,6 +1615,14 @@ int f3d_session_remesh(f3d_session *s, const f3d_session_remesh_desc *desc, char
         DeviceGuard g(checked(s).device);
         if (!desc) fail(F3D_STATUS_VALUE, "null re-mesh descriptor");
         remesh(*s, *desc);
+    });
+}
+
+int f3d_session_reterrain(f3d_session *s, const f3d_session_reterrain_desc *desc, char *err, size_t errlen) {
+    return c_abi(err, errlen, [&] {
+        DeviceGuard g(checked(s).device);
+        if (!desc) fail(F3D_STATUS_VALUE, "null re-terrain descriptor");
+        reterrain(*s, *desc);
     });
 }
 

@@ -263,8 +263,26 @@ def render_terrain_mesh_sequence(heightmap: "np.ndarray", width: int, height: in
     yield from _render_sequence("render_terrain_mesh_sequence", heightmap, width, height, camera, frames, common, False, True)
 
 
-def _render_sequence(name, heightmap, width, height, camera, frames, common, camera_per_frame: bool, mesh_per_frame: bool = False):
-    """The sequence generators: one session, re-armed (camera_per_frame: re-aimed; mesh_per_frame: re-meshed) between frames."""
+def render_terrain_dem_sequence(heightmap: "np.ndarray", width: int, height: int, camera: "dict | None" = None, *,
+                                frames: "Sequence[Mapping[str, Any]]", **common):
+    """Generator: item i equals ``hybrid_render_terrain_reference(frames[i]["heightmap"], width, height, camera_i, **common,
+    **rest_of_frames[i])`` -- ground that moves: a glacier, lava or flood time-lapse, an erosion or excavation run, a
+    sweep of the exaggeration.
+
+    ``frames[i]`` may hold ``"heightmap"`` (a DEM of the positional one's shape; without it the positional ``heightmap``),
+    optionally ``"exaggeration"`` (without it ``common``'s), optionally ``"camera"`` (camera_i; without it the positional
+    ``camera``) and any of SEQUENCE_FRAME_KEYS.  Every frame is checked by the wrapper's own rules before any device work,
+    and a frame whose DEM has another shape is refused (another DEM size needs a new session); then ONE session renders the
+    whole sequence, re-terrained between frames (f3d_session_reterrain: the samples uploaded in stream order, the
+    session's tables patched on the GPU) wherever the DEM or the exaggeration changes.
+    """
+    yield from _render_sequence("render_terrain_dem_sequence", heightmap, width, height, camera, frames, common, False, dem_per_frame=True)
+
+
+def _render_sequence(name, heightmap, width, height, camera, frames, common, camera_per_frame: bool, mesh_per_frame: bool = False,
+                     dem_per_frame: bool = False):
+    """The sequence generators: one session, re-armed (camera_per_frame: re-aimed; mesh_per_frame: re-meshed; dem_per_frame:
+    re-terrained) between frames."""
     import inspect
 
     from .session import TerrainSession
@@ -282,21 +300,28 @@ def _render_sequence(name, heightmap, width, height, camera, frames, common, cam
                 raise ValueError(f"frames[{i}] lacks 'camera': every frame of {name} names its camera (a sequence under "
                                  "one camera is render_terrain_sequence's)")
             cameras.append(frame.pop("camera"))
-        elif mesh_per_frame and "camera" in frame:
+        elif (mesh_per_frame or dem_per_frame) and "camera" in frame:
             cameras.append(frame.pop("camera"))
         else:
             cameras.append(camera)
         for key in frame:
             if mesh_per_frame and key in ("mesh_vertices", "mesh_indices"):
                 continue
+            if dem_per_frame and key in ("heightmap", "exaggeration"):
+                continue
             if key not in SEQUENCE_FRAME_KEYS:
                 raise ValueError(f"frames[{i}] sets {key!r}, which a live session cannot change (per-frame keys: "
                                  f"{', '.join(SEQUENCE_FRAME_KEYS)}); render it with hybrid_render_terrain_reference")
     if getattr(_NATIVE, "hybrid_render_terrain_reference", None) is None:
         raise RuntimeError("hybrid_render_terrain_reference requires the native forge3d module with GPU support")
-    calls = [_prepare(heightmap, width, height, cam, {**defaults, **common, **frame}) for cam, frame in zip(cameras, frames)]
+    dems = [frame.pop("heightmap", heightmap) if dem_per_frame else heightmap for frame in frames]
+    calls = [_prepare(dem, width, height, cam, {**defaults, **common, **frame}) for dem, cam, frame in zip(dems, cameras, frames)]
     if not calls:
         return
+    for i, (request, _, _) in enumerate(calls):
+        if request.dem.shape != calls[0][0].dem.shape:
+            raise ValueError(f"frames[{i}] has a heightmap of shape {request.dem.shape}, the sequence's DEM has {calls[0][0].dem.shape}: "
+                             "a live session keeps its DEM size (render it with hybrid_render_terrain_reference)")
     request, _, first = calls[0]
     native = dict(first)
     native.pop("certificate")
@@ -305,16 +330,20 @@ def _render_sequence(name, heightmap, width, height, camera, frames, common, cam
     session = TerrainSession(request.dem, request.width, request.height, request.camera,
                              frames_in_flight=_NATIVE_MODULE.FRAMES_IN_FLIGHT_AUTO, **native)
     held = (first["mesh_vertices"], first["mesh_indices"])  # the mesh the session holds
+    held_dem = (request.dem, first["exaggeration"])  # the DEM and exaggeration the session holds
     try:
         for i, (request, sun, keywords) in enumerate(calls):
             if i:
                 values = {key: keywords[key] for key in TerrainSession.REARMABLE if key in keywords}
                 mesh = (keywords["mesh_vertices"], keywords["mesh_indices"])
-                if mesh_per_frame and not (np.array_equal(mesh[0], held[0]) and np.array_equal(mesh[1], held[1])):
+                if dem_per_frame and not (keywords["exaggeration"] == held_dem[1] and np.array_equal(request.dem.view(np.uint32), held_dem[0].view(np.uint32))):  # (by bits: -0.0 is another DEM)
+                    session.reterrain(request.dem, request.camera, exaggeration=keywords["exaggeration"], **values)
+                    held_dem = (request.dem, keywords["exaggeration"])
+                elif mesh_per_frame and not (np.array_equal(mesh[0], held[0]) and np.array_equal(mesh[1], held[1])):
                     # this frame's mesh (its own or common's) on the topology the session holds: a refit; else the create's path
                     session.remesh(mesh[0], None if np.array_equal(mesh[1], held[1]) else mesh[1], request.camera, **values)
                     held = mesh
-                elif mesh_per_frame or camera_per_frame:
+                elif mesh_per_frame or camera_per_frame or dem_per_frame:
                     session.reaim(request.camera, **values)
                 else:
                     session.rearm(**values)

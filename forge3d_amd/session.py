@@ -64,7 +64,8 @@ class TerrainSession:
                        "observer_latitude_deg": float(desc.observer_latitude_deg),
                        "observer_longitude_deg": float(desc.observer_longitude_deg),
                        "pressure_mbar": float(desc.pressure_mbar), "temperature_c": float(desc.temperature_c)}
-        self._camera = dict(camera or {})  # what remesh() keeps when no camera is given
+        self._camera = dict(camera or {})  # what remesh() and reterrain() keep when no camera is given
+        self.dem_shape = (int(desc.dem_height), int(desc.dem_width))
         self.row_begin = int(row_begin)
         self.row_end = int(row_end) or int(height)
         self.rows = self.row_end - self.row_begin
@@ -156,6 +157,48 @@ class TerrainSession:
         self._check(self._lib.f3d_session_remesh(self._handle, C.byref(m), self._err, len(self._err)))
         del mv, mi
         self._note_armed(m.aim.arm)
+        if camera is not None:
+            self._camera = dict(camera)
+
+    def reterrain(self, heightmap, camera=None, *, at=None, exaggeration=None, **rearmable):
+        """reaim() under new DEM samples: what ``TerrainSession(resulting_dem, ..., camera=camera, exaggeration=..., **values)``
+        renders, on this session.  ``heightmap`` is the whole DEM (``at`` None: it must have the session's DEM shape) or a 2-D
+        patch whose first sample lies at DEM sample ``at=(row, col)``.  The samples are uploaded in stream order and the
+        session's own acceleration tables are patched on the GPU over the patch's footprint -- no host hash, no table build,
+        no wait, nothing allocated after the first call of a patch size.  ``exaggeration`` None keeps the session's; another
+        value rescales every sample and needs the whole DEM.  ``camera`` None keeps the current one (and the current
+        exposure); otherwise it is read as reaim() reads it.  DEM size and spacing stay the session's.  Same contract as
+        reaim(): a refused value leaves the session as it was, rendering the old terrain."""
+        unknown = [k for k in rearmable if k not in self.REARMABLE]
+        if unknown:
+            raise TypeError(f"reterrain() got an unexpected keyword argument {unknown[0]!r}")
+        block = np.ascontiguousarray(heightmap, dtype=np.float32)
+        if block.ndim != 2:
+            raise ValueError(f"heightmap must be 2D (H, W), got shape {block.shape}")
+        if at is None:
+            if block.shape != self.dem_shape:
+                raise ValueError(f"heightmap has shape {block.shape}, the session's DEM has {self.dem_shape}: a patch needs at=(row, col), "
+                                 "another DEM size needs a new session")
+            row, col = 0, 0
+        else:
+            row, col = (int(v) for v in at)
+            if row < 0 or col < 0:
+                raise ValueError(f"at=(row, col) must not be negative, got {tuple(at)}")
+        t = _native.ReterrainDesc()
+        t.struct_size = C.sizeof(_native.ReterrainDesc)
+        t.heights = block.ctypes.data
+        t.height, t.width = block.shape
+        t.y0, t.x0 = row, col
+        t.exaggeration = 0.0 if exaggeration is None else float(exaggeration)
+        if exaggeration is not None and float(exaggeration) == 0.0:
+            t.exaggeration = float("nan")  # (0 means "keep" in the C ABI; a zero exaggeration is the create's refusal)
+        if camera is None:
+            t.aim = self._reaim_desc(self._camera, dict(rearmable, exposure=rearmable.get("exposure", self._armed["exposure"])))
+        else:
+            t.aim = self._reaim_desc(camera, rearmable)
+        self._check(self._lib.f3d_session_reterrain(self._handle, C.byref(t), self._err, len(self._err)))
+        del block
+        self._note_armed(t.aim.arm)
         if camera is not None:
             self._camera = dict(camera)
 

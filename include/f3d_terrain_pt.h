@@ -311,7 +311,7 @@ int f3d_session_setup_ms(f3d_session *session, double *out, uint32_t count);
  * per-pixel sun-ray certificates (recomputed from the resident G-buffer, the camera rays are not traced again), the
  * AETHER record's sun terms, and the per-render state (accumulation, Welford, both reservoir buffers with their halo
  * rows -- caller-owned ones included --, head records, tile costs, stats), cleared as a new session has them.  Camera,
- * DEM, exaggeration, spacing, mesh (see f3d_session_remesh), environment map, image size, strip rows, spp, earth / refraction model and
+ * DEM and exaggeration (see f3d_session_reterrain), spacing, mesh (see f3d_session_remesh), environment map, image size, strip rows, spp, earth / refraction model and
  * atmosphere LUTs stay the session's; observer latitude / longitude, pressure and temperature are re-armable (they
  * only enter the curvature of the secondary rays).  The next frames render exactly what a new session created with
  * these values renders.  Added without an ABI version bump (no existing struct or signature changed): a binding
@@ -343,8 +343,8 @@ int f3d_session_certificates(f3d_session *session, uint64_t out[2]);
  * certificates (f3d_session_primary_start keeps returning the same pointer: its contents are the new view's after the
  * pass), sun-ray certificates.  One pass (k_reaim) traces the centre rays again, computes each sun certificate once and
  * clears the per-render state as the re-arm pass does; the longest-first tile order restarts from image order.  The
- * AETHER post reads the camera height and the pixel rays from the uniforms at resolve time, so it follows.  DEM,
- * exaggeration, spacing, mesh (see f3d_session_remesh), environment map, image size, strip rows and spp stay the session's.  The next frames
+ * AETHER post reads the camera height and the pixel rays from the uniforms at resolve time, so it follows.  DEM and
+ * exaggeration (see f3d_session_reterrain), spacing, mesh (see f3d_session_remesh), environment map, image size, strip rows and spp stay the session's.  The next frames
  * render exactly what a new session created with this camera and these values renders.  No ABI version bump: detected by
  * the symbol f3d_session_reaim. */
 typedef struct f3d_session_reaim_desc {
@@ -389,6 +389,39 @@ typedef struct f3d_session_remesh_desc {
     f3d_session_reaim_desc aim;   /* camera + everything a re-arm takes, same meaning */
 } f3d_session_remesh_desc;
 int f3d_session_remesh(f3d_session *session, const f3d_session_remesh_desc *desc, char *err, size_t errlen);
+/* ---- re-terrain: a re-aim under new DEM samples -------------------------------------------------------------------------
+ * What new heights change on top of a re-aim, still without a new session: the ground itself -- a time-lapse, an erosion
+ * or excavation step, a cut-and-fill edit, another exaggeration -- and with it everything the re-aim pass recomputes
+ * (centre hits, normals, depth, both certificates).  The update is a BLOCK of samples: width x height at DEM sample
+ * (x0, y0), row-major with pitch = width; the whole DEM is the block (0, 0, dem_width, dem_height).  It is uploaded in
+ * stream order into a staging buffer of the session and two kernels patch the session's OWN leaf table and band tables
+ * (f3d_retable.h): the cells with a corner in the block get exactly those corners replaced by height * exaggeration and
+ * their level-0 band, then every band level is rebuilt over the block's footprint from the level below -- the bits the
+ * create's builders produce, two launches whatever the DEM's size, no raw-height copy, no node table.  Asynchronous on
+ * the session stream behind everything enqueued so far, no wait for the device (a block above 8 MiB goes through the
+ * library's two 4 MiB pinned staging buffers more than once: its third chunk waits for its first).  The FIRST call gives the session its
+ * own tables (filled from the scene-cache entry by device copies; that entry, which other sessions and later creates
+ * share, is never written); only that call, and a call whose block is larger than any before (the staging buffer grows),
+ * allocate, against memory_budget_bytes (too small: refused, status 2); gpu_resource_bytes then exceeds a fresh session's
+ * by the staging buffer.
+ * exaggeration: 0 keeps the session's; another value rescales every sample, so it is accepted only with the whole DEM.
+ * DEM size and spacing stay the session's.  Validated by the create's code with its messages and statuses (a non-finite
+ * sample: "terrain heightfield contains non-finite samples", status 3; an exaggeration or a camera the create refuses:
+ * its text, status 2); a refusal leaves the session unchanged, usable and rendering the old terrain.  Refused with status
+ * 1: another struct_size, an empty block or one that leaves the DEM, a new exaggeration with a partial block, connected
+ * peer halos, a session whose occlusion rays march a mesh grid (F3D_MESH_FUSED builds), a session that built the opt-in
+ * far-horizon table (F3D_IBL_HORIZON=1: it would be stale).  The next frames render exactly what a new session created
+ * with the resulting DEM, this camera and these values renders.  No ABI version bump: detected by the symbol
+ * f3d_session_reterrain. */
+typedef struct f3d_session_reterrain_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_reterrain_desc) of the caller's header */
+    const float *heights;        /* HOST, the block, row-major, pitch = width; read during the call only */
+    uint32_t width, height;      /* of the block, >= 1 */
+    uint32_t x0, y0;             /* DEM sample of the block's first sample */
+    float exaggeration;          /* 0: keep; another value only with the whole DEM */
+    f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
+} f3d_session_reterrain_desc;
+int f3d_session_reterrain(f3d_session *session, const f3d_session_reterrain_desc *desc, char *err, size_t errlen);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);

@@ -12,6 +12,6 @@ KERNEL_FLAGS=${KERNEL_FLAGS-}
 /opt/rocm/bin/hipcc $COMMON $KERNEL_FLAGS "$@" -c forge3d_amd/csrc/f3d_kernels.hip -o build_ab/f3d_kernels_$NAME.o 2> build_ab/$NAME.err
 /opt/rocm/bin/hipcc $COMMON -shared "$@" build_ab/f3d_kernels_$NAME.o \
     forge3d_amd/csrc/f3d_host.hip forge3d_amd/csrc/f3d_denoise.hip forge3d_amd/csrc/f3d_smoke.hip forge3d_amd/csrc/f3d_smoke_sim.hip forge3d_amd/csrc/f3d_composite.hip \
-    forge3d_amd/csrc/f3d_lbvh.hip forge3d_amd/csrc/f3d_bvh_refit.hip forge3d_amd/csrc/f3d_wavefront.hip forge3d_amd/csrc/f3d_aether_bake.hip forge3d_amd/csrc/f3d_aether_ref.hip -o build_ab/libf3dhip_$NAME.so 2>> build_ab/$NAME.err
+    forge3d_amd/csrc/f3d_lbvh.hip forge3d_amd/csrc/f3d_bvh_refit.hip forge3d_amd/csrc/f3d_retable.hip forge3d_amd/csrc/f3d_wavefront.hip forge3d_amd/csrc/f3d_aether_bake.hip forge3d_amd/csrc/f3d_aether_ref.hip -o build_ab/libf3dhip_$NAME.so 2>> build_ab/$NAME.err
 rm -f build_ab/f3d_kernels_$NAME.o
 ls -la build_ab/libf3dhip_$NAME.so
