@@ -101,9 +101,19 @@ struct f3d_session {
         void *nodes = nullptr;
         uint32_t *parent = nullptr, *counter = nullptr;
         int *bounds = nullptr;
-        size_t vertex_bytes = 0, tri_bytes = 0, node_bytes = 0, table_bytes = 0;
+        size_t vertex_bytes = 0, tri_bytes = 0, node_bytes = 0, link_bytes = 0 /* parent, counter: each */, bounds_bytes = 0;
         uint32_t refits = 0;
         bool live = false;
+        uint64_t bytes() const { return (uint64_t)vertex_bytes + tri_bytes + node_bytes + 2u * link_bytes + bounds_bytes; }
+        void release(Ledger &mem) {  // (a buffer the mesh has no use for is null: Ledger::free passes it over)
+            mem.free(vertices, vertex_bytes);
+            mem.free(tris, tri_bytes);
+            mem.free(nodes, node_bytes);
+            mem.free(parent, link_bytes);
+            mem.free(counter, link_bytes);
+            mem.free(bounds, bounds_bytes);
+            *this = OwnMesh{};
+        }
     } own_mesh;
     // re-terrain (f3d_session_reterrain): what of mem.device_bytes stands for the shared scene entry, and -- from the first
     // re-terrain on -- the session's own leaf and band tables (TableLayout sizes; `tables` and params.terrain then name
@@ -285,23 +295,17 @@ void upload_aether(f3d_session &s, const f3d_aether_luts &L, const f3d_terrain_r
 
 // A caller compiled against another revision of the header passes structs of another size: refuse them before a
 // single member is read (include/f3d_terrain_pt.h F3D_ABI_VERSION).
-void check_abi(const f3d_terrain_ref_desc *d, const f3d_session_opts *opts) {
-    char msg[256];
-    if (d && d->struct_size != sizeof(f3d_terrain_ref_desc)) {
-        snprintf(msg, sizeof msg, "f3d_terrain_ref_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
-                 "was built against another revision of f3d_terrain_pt.h", d->struct_size, F3D_ABI_VERSION, sizeof(f3d_terrain_ref_desc));
-        fail(F3D_STATUS_VALUE, msg);
-    }
-    if (opts && opts->struct_size != sizeof(f3d_session_opts)) {
-        snprintf(msg, sizeof msg, "f3d_session_opts.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
-                 "was built against another revision of f3d_terrain_pt.h", opts->struct_size, F3D_ABI_VERSION, sizeof(f3d_session_opts));
-        fail(F3D_STATUS_VALUE, msg);
-    }
+template <class T>
+void check_struct_size(const T &d, const char *name) {
+    if (d.struct_size != sizeof(T))
+        fail(F3D_STATUS_VALUE, "%s.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
+             "was built against another revision of f3d_terrain_pt.h", name, d.struct_size, F3D_ABI_VERSION, sizeof(T));
 }
 
 void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_session_opts *opts) {
     SetupClock clock(s.setup_ms);
-    check_abi(&d, opts);
+    check_struct_size(d, "f3d_terrain_ref_desc");
+    if (opts) check_struct_size(*opts, "f3d_session_opts");
     validate_desc(d);
     // every DEM sample is looked at ONCE: finiteness (validate_scene) and the scene cache's key come out of one pass
     DemFingerprint fp;
@@ -877,359 +881,6 @@ void resolve(f3d_session &s, uint32_t frames, uint8_t *d_rgba, float *d_albedo, 
     hip_check(launch_resolve(R, s.stream), "resolve kernel");
 }
 
-// A new render on a live session under another sun / seed / exposure / IBL intensity / frame budget, and (re-aim: cam
-// given) another camera: the descriptor's re-armable members replaced, validated and turned into uniforms by the
-// create's own code (validate_desc, fill_uniforms), then k_rearm -- or, for a new camera, k_reaim -- on the session
-// stream behind everything enqueued so far.  Nothing is allocated, nothing waits for the device.  A refused descriptor
-// leaves the session as it was.
-// (rearm_desc: the checks that need no scene and the descriptor with the new members; rearm_apply: uniforms, pass, host
-// state.  f3d_session_remesh puts its mesh step between the validation and rearm_apply.)
-f3d_terrain_ref_desc rearm_desc(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_reaim_desc *cam, const char *done) {
-    if (cam && cam->struct_size != sizeof(f3d_session_reaim_desc))
-        fail(F3D_STATUS_VALUE, "f3d_session_reaim_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
-             "was built against another revision of f3d_terrain_pt.h", cam->struct_size, F3D_ABI_VERSION, sizeof(f3d_session_reaim_desc));
-    if (r.struct_size != sizeof(f3d_session_rearm_desc))
-        fail(F3D_STATUS_VALUE, "f3d_session_rearm_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
-             "was built against another revision of f3d_terrain_pt.h", r.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_rearm_desc));
-    if (s.peer[0].connected || s.peer[1].connected)
-        fail(F3D_STATUS_VALUE, "a session with peer halos cannot be %s: the frame counters its neighbours poll only rise", done);
-    f3d_terrain_ref_desc d = s.desc;
-    d.sun_azimuth_deg = r.sun_azimuth_deg;
-    d.sun_elevation_deg = r.sun_elevation_deg;
-    d.sun_intensity = r.sun_intensity;
-    for (int c = 0; c < 3; c++) d.sun_color[c] = r.sun_color[c];
-    d.exposure = r.exposure;
-    d.env_intensity = r.env_intensity;
-    d.seed = r.seed;
-    d.max_frames = r.max_frames;
-    d.min_frames = r.min_frames;
-    d.variance_threshold = r.variance_threshold;
-    d.observer_latitude_deg = r.observer_latitude_deg;
-    d.observer_longitude_deg = r.observer_longitude_deg;
-    d.pressure_mbar = r.pressure_mbar;
-    d.temperature_c = r.temperature_c;
-    if (cam) {
-        for (int c = 0; c < 3; c++) {
-            d.cam_origin[c] = cam->cam_origin[c];
-            d.cam_look_at[c] = cam->cam_look_at[c];
-            d.cam_up[c] = cam->cam_up[c];
-        }
-        d.fov_y_deg = cam->fov_y_deg;
-    }
-    return d;
-}
-
-// d: validated; U / require_valid: fill_uniforms(d, U)
-void rearm_apply(f3d_session &s, const f3d_terrain_ref_desc &d, const FrameParams &U, bool require_valid, bool cam, double t_host) {
-    // (DEM transform, spacing and spp are the create's, and without a re-aim the camera: fill_uniforms gives them the same
-    // bits again.  The AETHER post reads the camera from these uniforms at resolve time: its record holds no camera term.)
-    FrameParams &P = s.params;
-    P.cam = U.cam;
-    P.light = U.light;
-    P.terrain.inv_two_r_prime = U.terrain.inv_two_r_prime;
-    P.terrain.curvature_enabled = U.terrain.curvature_enabled;
-    P.env.intensity = U.env.intensity;
-    P.same_sun = same_sun_of(P);
-    if (s.aether.enabled) aether_sun_terms(s.aether, d);
-    s.require_valid_reservoirs = require_valid;
-    s.desc = d;
-    s.desc.mesh_vertices = nullptr;  // (a re-mesh validated them through d: read during the call only)
-    s.desc.mesh_indices = nullptr;
-
-    join_bands(s);  // (the session stream after every band launch so far: the clears follow the last frame's kernels)
-    P.band_begin = s.row_begin;
-    P.band_end = s.row_end;
-    P.frame_index = 0;
-    P.trace_first = 0u;
-    P.res_in = s.res[1];
-    P.res_out = s.res[0];
-    P.collect_stats = 0;
-    P.tile_order = nullptr;
-    P.tile_cost = nullptr;
-    RearmParams R{};
-    R.frame = P;
-    R.gbuffer_n = s.gbuffer_n;
-    R.depth = s.depth;
-    R.res[0] = s.res[0];
-    R.res[1] = s.res[1];
-    R.tile_cost = s.tile_cost;
-    R.tiles = s.tile_cost ? frame_tile_count(P, nullptr) : 0u;
-    if (cam) hip_check(launch_reaim(R, s.stream), "re-aim kernel");
-    else hip_check(launch_rearm(R, s.stream), "re-arm kernel");
-    // host-side frame state as a new session has it
-    s.cost_frame = s.order_frame = -1;
-    s.rendered = false;
-    s.trace_first = -1;
-    s.trace_count = 0;
-    for (auto &b : s.bands) {
-        b.last = -1;
-        b.unjoined = false;
-    }
-    s.reaim_seconds = cam ? now_s() - t_host : 0.0;
-}
-
-void rearm(f3d_session &s, const f3d_session_rearm_desc &r, const f3d_session_reaim_desc *cam = nullptr) {
-    const double t_host = now_s();
-    const f3d_terrain_ref_desc d = rearm_desc(s, r, cam, cam ? "re-aimed" : "re-armed");
-    validate_desc(d);
-    FrameParams U{};
-    const bool require_valid = fill_uniforms(d, U);
-    rearm_apply(s, d, U, require_valid, cam != nullptr, t_host);
-}
-
-// ---- re-mesh: the mesh of a live session moved (refit) or replaced (the create's path), then a re-aim ------------------
-// Positions only: the session's own copy of vertices, leaf-order triangles and nodes (made at the first refit; the cache
-// entry other sessions share is never written), the vertex upload in stream order, then the refit passes of
-// f3d_bvh_refit.h -- all on the session stream behind everything enqueued so far, no wait for the device.
-void remesh_refit(f3d_session &s, const float *vertices, uint32_t vertex_count) {
-    FrameParams &P = s.params;
-    f3d_session::OwnMesh &O = s.own_mesh;
-    const CachedMesh &E = *s.mesh;
-    const bool first = !O.live;
-    const uint32_t nodes = E.dev.bvh4_nodes ? E.dev.bvh4_node_count : E.dev.bvh_node_count;
-    if (first) {
-        f3d_session::OwnMesh N;
-        N.vertex_bytes = E.vertex_bytes;
-        N.tri_bytes = E.tri_bytes;
-        N.node_bytes = E.node_bytes;
-        N.table_bytes = 2u * (size_t)std::max(nodes, 1u) * sizeof(uint32_t) + 12u * sizeof(int);
-        // the count drops the shared entry's bytes and adds the private ones (the indices stay the entry's)
-        const uint64_t planned = s.mem.device_bytes - s.mesh_counted + E.index_bytes + N.vertex_bytes + N.tri_bytes + N.node_bytes + N.table_bytes;
-        if (planned > s.budget)
-            fail(F3D_STATUS_RENDER,
-                 "re-mesh exceeds the memory budget: the session's own copy of the mesh and the refit tables bring the tracked total to "
-                 "%llu > limit %llu", (unsigned long long)planned, (unsigned long long)s.budget);
-        std::vector<std::pair<void *, size_t>> got;
-        auto take = [&](size_t bytes, const char *what) {
-            void *p = s.mem.alloc(bytes, what);
-            got.emplace_back(p, bytes);
-            return p;
-        };
-        try {
-            N.vertices = (float4 *)take(N.vertex_bytes, "re-mesh vertices");
-            if (N.tri_bytes) N.tris = (float4 *)take(N.tri_bytes, "re-mesh BVH triangles");
-            if (N.node_bytes) N.nodes = take(N.node_bytes, "re-mesh BVH nodes");
-            N.parent = (uint32_t *)take((size_t)std::max(nodes, 1u) * sizeof(uint32_t), "re-mesh parent links");
-            N.counter = (uint32_t *)take((size_t)std::max(nodes, 1u) * sizeof(uint32_t), "re-mesh arrival counters");
-            N.bounds = (int *)take(12u * sizeof(int), "re-mesh scene bounds");
-        } catch (...) {
-            for (auto &g : got) s.mem.free(g.first, g.second);
-            throw;
-        }
-        s.mem.device_bytes -= s.mesh_counted;
-        s.mesh_counted = E.index_bytes;
-        s.mem.device_bytes += s.mesh_counted;
-        join_bands(s);
-        // topology words and the triangles' index words from the shared entry; counters at zero; both bound sets empty
-        if (N.tris) hip_check(hipMemcpyAsync(N.tris, E.dev.bvh_tris, N.tri_bytes, hipMemcpyDeviceToDevice, s.stream), "re-mesh copy");
-        if (N.nodes)
-            hip_check(hipMemcpyAsync(N.nodes, E.dev.bvh4_nodes ? (const void *)E.dev.bvh4_nodes : (const void *)E.dev.bvh_nodes, N.node_bytes,
-                                     hipMemcpyDeviceToDevice, s.stream), "re-mesh copy");
-        hip_check(hipMemsetAsync(N.counter, 0, (size_t)std::max(nodes, 1u) * sizeof(uint32_t), s.stream), "re-mesh counters");
-        static const int kEmptyBounds[12] = {0x7F800000, 0x7F800000, 0x7F800000, (int)0x807FFFFF, (int)0x807FFFFF, (int)0x807FFFFF,
-                                             0x7F800000, 0x7F800000, 0x7F800000, (int)0x807FFFFF, (int)0x807FFFFF, (int)0x807FFFFF};
-        hip_check(hipMemcpyAsync(N.bounds, kEmptyBounds, sizeof(kEmptyBounds), hipMemcpyHostToDevice, s.stream), "re-mesh bounds");
-        N.live = true;
-        O = N;
-        P.mesh.vertices = O.vertices;
-        if (O.tris) P.mesh.bvh_tris = O.tris;
-        if (O.nodes && E.dev.bvh4_nodes) P.mesh.bvh4_nodes = (const Bvh4Node *)O.nodes;
-        else if (O.nodes) P.mesh.bvh_nodes = (const BvhNode *)O.nodes;
-    } else {
-        join_bands(s);
-    }
-    const std::vector<float> v4 = pad_rgb_to_rgba(vertices, vertex_count, 0.0f);
-    upload_staged(O.vertices, v4.data(), v4.size() * sizeof(float), s.stream, true);
-    RefitParams R{};
-    R.vertices = O.vertices;
-    R.indices = E.dev.indices;
-    R.tris = O.tris;
-    R.tri_count = O.tris ? E.index_count / 3u : 0u;
-    if (E.dev.bvh4_nodes) {
-        R.wide = (Bvh4Node *)O.nodes;
-        R.wide_count = nodes;
-    } else {
-        R.nodes = (BvhNode *)O.nodes;
-        R.node_count = nodes;
-    }
-    R.parent = O.parent;
-    R.counter = O.counter;
-    R.bounds = O.bounds + 6u * (O.refits & 1u);
-    R.bounds_next = O.bounds + 6u * ((O.refits & 1u) ^ 1u);
-    hip_check(launch_bvh_refit(R, first, s.stream), "BVH refit kernels");
-    O.refits++;
-}
-
-// Another mesh: the create's path with the session's builder (cache, host SAH or LBVH; may wait and allocate like a create).
-void remesh_replace(f3d_session &s, const f3d_terrain_ref_desc &d) {
-    FrameParams &P = s.params;
-    f3d_session::OwnMesh &O = s.own_mesh;
-    std::shared_ptr<CachedMesh> fresh = acquire_mesh(s.device, d.mesh_vertices, d.mesh_vertex_count, d.mesh_indices, d.mesh_index_count,
-                                                     s.mesh_builder, s.stream);
-    const uint64_t own = O.live ? (uint64_t)O.vertex_bytes + O.tri_bytes + O.node_bytes + O.table_bytes : 0u;
-    const uint64_t planned = s.mem.device_bytes - s.mesh_counted - own + fresh->mem.device_bytes;
-    if (planned > s.budget)
-        fail(F3D_STATUS_RENDER, "re-mesh exceeds the memory budget: the new mesh brings the tracked total to %llu > limit %llu",
-             (unsigned long long)planned, (unsigned long long)s.budget);
-    // the old mesh goes only after the work enqueued before this call has finished
-    join_bands(s);
-    hip_check(hipStreamSynchronize(s.stream), "re-mesh");
-    if (O.live) {
-        const uint32_t nodes = s.mesh->dev.bvh4_nodes ? s.mesh->dev.bvh4_node_count : s.mesh->dev.bvh_node_count;
-        const size_t table = (size_t)std::max(nodes, 1u) * sizeof(uint32_t);
-        s.mem.free(O.vertices, O.vertex_bytes);
-        if (O.tris) s.mem.free(O.tris, O.tri_bytes);
-        if (O.nodes) s.mem.free(O.nodes, O.node_bytes);
-        s.mem.free(O.parent, table);
-        s.mem.free(O.counter, table);
-        s.mem.free(O.bounds, 12u * sizeof(int));
-        O = f3d_session::OwnMesh{};
-    }
-    s.mem.device_bytes -= s.mesh_counted;
-    s.mesh = fresh;
-    s.mesh_counted = fresh->mem.device_bytes;
-    s.mem.device_bytes += s.mesh_counted;
-    P.mesh = fresh->dev;
-}
-
-void remesh(f3d_session &s, const f3d_session_remesh_desc &m) {
-    if (m.struct_size != sizeof(f3d_session_remesh_desc))
-        fail(F3D_STATUS_VALUE, "f3d_session_remesh_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
-             "was built against another revision of f3d_terrain_pt.h", m.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_remesh_desc));
-    const double t_host = now_s();
-    f3d_terrain_ref_desc d = rearm_desc(s, m.aim.arm, &m.aim, "re-meshed");
-    if (!s.mesh)
-        fail(F3D_STATUS_VALUE, "this session was created without a mesh: a re-mesh moves or replaces a session's mesh, it cannot give it one");
-    if (s.mesh_grid)
-        fail(F3D_STATUS_VALUE, "this session's occlusion rays march a mesh grid made from the create's mesh (F3D_MESH_FUSED build): it cannot be re-meshed");
-    if (m.mesh_indices) {  // another mesh: every mesh check of the create
-        d.mesh_vertices = m.mesh_vertices;
-        d.mesh_vertex_count = m.mesh_vertex_count;
-        d.mesh_indices = m.mesh_indices;
-        d.mesh_index_count = m.mesh_index_count;
-    } else {  // positions only: the create's vertex checks, with its texts and statuses (validate_desc, f3d_setup.h)
-        if (!m.mesh_vertices || m.mesh_vertex_count == 0) fail(F3D_STATUS_RENDER, "mesh vertices must be a non-empty flat [x,y,z] list");
-        if (m.mesh_vertex_count != s.params.mesh.vertex_count)
-            fail(F3D_STATUS_VALUE, "a re-mesh without mesh_indices moves the session's mesh: %u vertices given, its topology has %u (pass "
-                 "mesh_indices for another mesh)", m.mesh_vertex_count, s.params.mesh.vertex_count);
-        for (size_t i = 0; i < (size_t)m.mesh_vertex_count * 3; i++)
-            if (!std::isfinite(m.mesh_vertices[i])) fail(F3D_STATUS_RENDER, "mesh vertices contain non-finite values");
-    }
-    validate_desc(d);
-    FrameParams U{};
-    const bool require_valid = fill_uniforms(d, U);
-    if (m.mesh_indices) remesh_replace(s, d);
-    else remesh_refit(s, m.mesh_vertices, m.mesh_vertex_count);
-    rearm_apply(s, d, U, require_valid, true, t_host);
-}
-
-// ---- re-terrain: new DEM samples on a live session, its tables patched on the GPU, then a re-aim -------------------------
-// The block is uploaded in stream order into the session's staging buffer and the two passes of f3d_retable.h patch the
-// session's OWN leaf and band tables (taken at the first call and filled from the shared scene-cache entry by device
-// copies; that entry is never written and stays referenced -- the copies read it -- but is no longer counted).  All on the
-// session stream behind everything enqueued so far, no wait for the device; only the first call, and a call with a block
-// larger than any before (the staging buffer grows: the old one goes back through the allocator, which waits for the work
-// that reads it), allocate.  Every refusal comes before the first change of the session.
-void reterrain(f3d_session &s, const f3d_session_reterrain_desc &t) {
-    if (t.struct_size != sizeof(f3d_session_reterrain_desc))
-        fail(F3D_STATUS_VALUE, "f3d_session_reterrain_desc.struct_size is %u, this library (ABI version %u) expects %zu: the caller "
-             "was built against another revision of f3d_terrain_pt.h", t.struct_size, F3D_ABI_VERSION, sizeof(f3d_session_reterrain_desc));
-    const double t_host = now_s();
-    f3d_terrain_ref_desc d = rearm_desc(s, t.aim.arm, &t.aim, "re-terrained");
-    if (s.mesh_grid)
-        fail(F3D_STATUS_VALUE, "this session's occlusion rays march a mesh grid binned on the create's terrain cells (F3D_MESH_FUSED build): it cannot be re-terrained");
-    if (s.params.terrain.horizon)
-        fail(F3D_STATUS_VALUE, "this session built the far-horizon table of its DEM (F3D_IBL_HORIZON=1): it cannot be re-terrained, the table would be stale");
-    const uint32_t w = s.desc.dem_width, h = s.desc.dem_height;
-    if (!t.heights || t.width == 0u || t.height == 0u)
-        fail(F3D_STATUS_VALUE, "re-terrain block is empty (%ux%u samples): a block holds at least one sample", t.width, t.height);
-    if (t.x0 >= w || t.y0 >= h || t.width > w - t.x0 || t.height > h - t.y0)
-        fail(F3D_STATUS_VALUE, "re-terrain block of %ux%u samples at sample (%u, %u) leaves the session's %ux%u DEM (another DEM size needs a new session)",
-             t.width, t.height, t.x0, t.y0, w, h);
-    const bool whole = t.x0 == 0u && t.y0 == 0u && t.width == w && t.height == h;
-    if (t.exaggeration != 0.0f && !(t.exaggeration == s.desc.exaggeration)) {
-        if (!whole)
-            fail(F3D_STATUS_VALUE, "a new exaggeration (%g, the session's is %g) rescales every sample: give it with the whole %ux%u DEM, not with a block",
-                 (double)t.exaggeration, (double)s.desc.exaggeration, w, h);
-        d.exaggeration = t.exaggeration;
-    }
-    validate_desc(d);
-    const size_t samples = (size_t)t.width * t.height, block_bytes = samples * sizeof(float);
-    {
-        uint32_t bad = 0u;  // (an exponent field of all ones: inf / NaN)
-        for (size_t i = 0; i < samples; i++) {
-            uint32_t v;
-            memcpy(&v, t.heights + i, sizeof v);
-            bad |= (uint32_t)((v & 0x7F800000u) == 0x7F800000u);
-        }
-        if (bad) fail(F3D_STATUS_UPLOAD, "terrain heightfield contains non-finite samples");
-    }
-    FrameParams U{};
-    const bool require_valid = fill_uniforms(d, U);
-
-    FrameParams &P = s.params;
-    f3d_session::OwnTerrain &O = s.own_terrain;
-    const TableLayout &L = s.tables.layout;
-    const size_t leaf_bytes = L.leaf_count * sizeof(LeafRec), band_bytes = L.band_count * sizeof(NodeRec);
-    const bool take_tables = !O.leaves, grow = block_bytes > O.staging_bytes;
-    if (take_tables || grow) {
-        // the count drops the shared entry's bytes and adds the own tables and the staging buffer
-        const uint64_t planned = s.mem.device_bytes - (take_tables ? s.scene_counted : 0u) + (take_tables ? leaf_bytes + band_bytes : 0u) -
-                                 (grow ? O.staging_bytes : 0u) + (grow ? block_bytes : 0u);
-        if (planned > s.budget)
-            fail(F3D_STATUS_RENDER,
-                 "re-terrain exceeds the memory budget: the session's own tables and the staging buffer of a %ux%u block bring the tracked total to "
-                 "%llu > limit %llu", t.width, t.height, (unsigned long long)planned, (unsigned long long)s.budget);
-        std::vector<std::pair<void *, size_t>> got;
-        auto take = [&](size_t bytes, const char *what) {
-            void *p = s.mem.alloc(bytes, what);
-            got.emplace_back(p, bytes);
-            return p;
-        };
-        f3d_session::OwnTerrain N = O;
-        try {
-            if (grow) N.staging = (float *)take(block_bytes, "re-terrain staging");
-            if (take_tables) {
-                N.leaves = (LeafRec *)take(leaf_bytes, "re-terrain leaf table");
-                N.bands = (NodeRec *)take(band_bytes, "re-terrain band tables");
-                N.leaf_bytes = leaf_bytes;
-                N.band_bytes = band_bytes;
-            }
-        } catch (...) {
-            for (auto &g : got) s.mem.free(g.first, g.second);
-            throw;
-        }
-        if (grow) {
-            if (O.staging) s.mem.free(O.staging, O.staging_bytes);
-            N.staging_bytes = block_bytes;
-        }
-        if (take_tables) {
-            s.mem.device_bytes -= s.scene_counted;
-            s.scene_counted = 0u;
-        }
-        O = N;
-    }
-    join_bands(s);
-    if (!O.live) {
-        hip_check(hipMemcpyAsync(O.leaves, s.tables.leaves, leaf_bytes, hipMemcpyDeviceToDevice, s.stream), "re-terrain copy");
-        hip_check(hipMemcpyAsync(O.bands, s.tables.bands, band_bytes, hipMemcpyDeviceToDevice, s.stream), "re-terrain copy");
-    }
-    upload_staged(O.staging, t.heights, block_bytes, s.stream, true);
-    hip_check(launch_retable(retable_params(L, O.staging, t.x0, t.y0, t.width, t.height, d.exaggeration, O.leaves, O.bands), s.stream),
-              "re-terrain table kernels");
-    if (!O.live) {
-        O.live = true;
-        s.tables.leaves = O.leaves;
-        s.tables.bands = O.bands;
-        s.tables.dev.leaves = O.leaves;
-        s.tables.dev.bands = O.bands;
-        P.terrain.leaves = O.leaves;
-        P.terrain.bands = O.bands;
-        P.terrain.mesh_bands = O.bands;  // (no mesh grid: refused above)
-    }
-    rearm_apply(s, d, U, require_valid, true, t_host);
-}
-
 // The accumulation loop of a whole-image session up to the readback (render_terrain.rs:1123-1404): windows of frames
 // until converged or capped, the final resolve (and AETHER post), the copies into the caller's buffers.  Everything of
 // f3d_terrain_ref_out but setup_seconds.
@@ -1300,6 +951,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 }  // namespace
 
 #include "f3d_host_halo.h"  // peer halos: the pull kernel, the batch enqueue and their C ABI
+#include "f3d_host_update.h"  // session updates (re-arm, re-aim, re-mesh, re-terrain): one path, their own steps and their C ABI
 
 // ---------------------------------------------------------------------------------------
 // C ABI
@@ -1592,38 +1244,6 @@ int f3d_session_fingerprint(f3d_session *s, uint64_t *out, uint32_t count) {
     } catch (...) {
         return F3D_STATUS_DEVICE;
     }
-}
-
-int f3d_session_rearm(f3d_session *s, const f3d_session_rearm_desc *desc, char *err, size_t errlen) {
-    return c_abi(err, errlen, [&] {
-        DeviceGuard g(checked(s).device);
-        if (!desc) fail(F3D_STATUS_VALUE, "null re-arm descriptor");
-        rearm(*s, *desc);
-    });
-}
-
-int f3d_session_reaim(f3d_session *s, const f3d_session_reaim_desc *desc, char *err, size_t errlen) {
-    return c_abi(err, errlen, [&] {
-        DeviceGuard g(checked(s).device);
-        if (!desc) fail(F3D_STATUS_VALUE, "null re-aim descriptor");
-        rearm(*s, desc->arm, desc);
-    });
-}
-
-int f3d_session_remesh(f3d_session *s, const f3d_session_remesh_desc *desc, char *err, size_t errlen) {
-    return c_abi(err, errlen, [&] {
-        DeviceGuard g(checked(s).device);
-        if (!desc) fail(F3D_STATUS_VALUE, "null re-mesh descriptor");
-        remesh(*s, *desc);
-    });
-}
-
-int f3d_session_reterrain(f3d_session *s, const f3d_session_reterrain_desc *desc, char *err, size_t errlen) {
-    return c_abi(err, errlen, [&] {
-        DeviceGuard g(checked(s).device);
-        if (!desc) fail(F3D_STATUS_VALUE, "null re-terrain descriptor");
-        reterrain(*s, *desc);
-    });
 }
 
 int f3d_session_render(f3d_session *s, f3d_terrain_ref_out *out, char *err, size_t errlen) {

@@ -147,6 +147,20 @@ struct Ledger {
         for (void *p : owned) (void)device_free(p);
         owned.clear();
     }
+    // Several buffers taken for one step: every one of them goes back unless commit() is reached (a later one did not fit).
+    struct Take {
+        Ledger &mem;
+        std::vector<std::pair<void *, size_t>> got;
+        ~Take() {
+            for (auto &g : got) mem.free(g.first, g.second);
+        }
+        void *operator()(size_t bytes, const char *what) {
+            void *p = mem.alloc(bytes, what);
+            got.emplace_back(p, bytes);
+            return p;
+        }
+        void commit() { got.clear(); }
+    };
 };
 
 // ---- acceleration tables, built on the GPU ----

@@ -229,7 +229,7 @@ def render_terrain_sequence(heightmap: "np.ndarray", width: int, height: int, ca
     refraction).  Every frame is checked by the wrapper's own rules before any device work; then ONE session renders the
     whole sequence, re-armed between frames (f3d_session_rearm: no new tables, allocations or G-buffer pass).
     """
-    yield from _render_sequence("render_terrain_sequence", heightmap, width, height, camera, frames, common, False)
+    yield from _render_sequence("render_terrain_sequence", heightmap, width, height, camera, frames, common)
 
 
 def render_terrain_camera_sequence(heightmap: "np.ndarray", width: int, height: int, *,
@@ -242,7 +242,7 @@ def render_terrain_camera_sequence(heightmap: "np.ndarray", width: int, height: 
     before any device work; then ONE session renders the whole sequence, re-aimed between frames (f3d_session_reaim: no
     new tables, allocations, streams or clears -- one pass traces the centre rays of the new view).
     """
-    yield from _render_sequence("render_terrain_camera_sequence", heightmap, width, height, None, frames, common, True)
+    yield from _render_sequence("render_terrain_camera_sequence", heightmap, width, height, None, frames, common)
 
 
 def render_terrain_mesh_sequence(heightmap: "np.ndarray", width: int, height: int, camera: "dict | None" = None, *,
@@ -260,7 +260,7 @@ def render_terrain_mesh_sequence(heightmap: "np.ndarray", width: int, height: in
     if common.get("mesh_vertices") is None or common.get("mesh_indices") is None:
         raise ValueError("render_terrain_mesh_sequence needs the mesh in the common keywords (mesh_vertices and mesh_indices): a "
                          "live session cannot be given a mesh it was created without")
-    yield from _render_sequence("render_terrain_mesh_sequence", heightmap, width, height, camera, frames, common, False, True)
+    yield from _render_sequence("render_terrain_mesh_sequence", heightmap, width, height, camera, frames, common)
 
 
 def render_terrain_dem_sequence(heightmap: "np.ndarray", width: int, height: int, camera: "dict | None" = None, *,
@@ -276,17 +276,26 @@ def render_terrain_dem_sequence(heightmap: "np.ndarray", width: int, height: int
     whole sequence, re-terrained between frames (f3d_session_reterrain: the samples uploaded in stream order, the
     session's tables patched on the GPU) wherever the DEM or the exaggeration changes.
     """
-    yield from _render_sequence("render_terrain_dem_sequence", heightmap, width, height, camera, frames, common, False, dem_per_frame=True)
+    yield from _render_sequence("render_terrain_dem_sequence", heightmap, width, height, camera, frames, common)
 
 
-def _render_sequence(name, heightmap, width, height, camera, frames, common, camera_per_frame: bool, mesh_per_frame: bool = False,
-                     dem_per_frame: bool = False):
-    """The sequence generators: one session, re-armed (camera_per_frame: re-aimed; mesh_per_frame: re-meshed; dem_per_frame:
-    re-terrained) between frames."""
+# generator -> (a frame must / may / may not hold "camera", its keys beyond SEQUENCE_FRAME_KEYS, the strongest update the generator
+# admits: a frame that does not need it falls through to a re-aim -- under "rearm", which has no per-frame camera, to a re-arm)
+_SEQUENCES = {
+    "render_terrain_sequence": ("may not", (), "rearm"),
+    "render_terrain_camera_sequence": ("must", (), "reaim"),
+    "render_terrain_mesh_sequence": ("may", ("mesh_vertices", "mesh_indices"), "remesh"),
+    "render_terrain_dem_sequence": ("may", ("heightmap", "exaggeration"), "reterrain"),
+}
+
+
+def _render_sequence(name, heightmap, width, height, camera, frames, common):
+    """The sequence generators: one session, updated between frames as _SEQUENCES[name] says."""
     import inspect
 
     from .session import TerrainSession
 
+    frame_camera, extra_keys, update = _SEQUENCES[name]
     signature = inspect.signature(hybrid_render_terrain_reference)
     defaults = {key: p.default for key, p in signature.parameters.items() if p.kind is inspect.Parameter.KEYWORD_ONLY}
     for key in common:
@@ -295,26 +304,17 @@ def _render_sequence(name, heightmap, width, height, camera, frames, common, cam
     frames = [dict(f) for f in frames]
     cameras = []
     for i, frame in enumerate(frames):
-        if camera_per_frame:
-            if "camera" not in frame:
-                raise ValueError(f"frames[{i}] lacks 'camera': every frame of {name} names its camera (a sequence under "
-                                 "one camera is render_terrain_sequence's)")
-            cameras.append(frame.pop("camera"))
-        elif (mesh_per_frame or dem_per_frame) and "camera" in frame:
-            cameras.append(frame.pop("camera"))
-        else:
-            cameras.append(camera)
+        if frame_camera == "must" and "camera" not in frame:
+            raise ValueError(f"frames[{i}] lacks 'camera': every frame of {name} names its camera (a sequence under "
+                             "one camera is render_terrain_sequence's)")
+        cameras.append(frame.pop("camera") if frame_camera != "may not" and "camera" in frame else camera)
         for key in frame:
-            if mesh_per_frame and key in ("mesh_vertices", "mesh_indices"):
-                continue
-            if dem_per_frame and key in ("heightmap", "exaggeration"):
-                continue
-            if key not in SEQUENCE_FRAME_KEYS:
+            if key not in extra_keys and key not in SEQUENCE_FRAME_KEYS:
                 raise ValueError(f"frames[{i}] sets {key!r}, which a live session cannot change (per-frame keys: "
                                  f"{', '.join(SEQUENCE_FRAME_KEYS)}); render it with hybrid_render_terrain_reference")
     if getattr(_NATIVE, "hybrid_render_terrain_reference", None) is None:
         raise RuntimeError("hybrid_render_terrain_reference requires the native forge3d module with GPU support")
-    dems = [frame.pop("heightmap", heightmap) if dem_per_frame else heightmap for frame in frames]
+    dems = [frame.pop("heightmap", heightmap) if "heightmap" in extra_keys else heightmap for frame in frames]
     calls = [_prepare(dem, width, height, cam, {**defaults, **common, **frame}) for dem, cam, frame in zip(dems, cameras, frames)]
     if not calls:
         return
@@ -336,17 +336,20 @@ def _render_sequence(name, heightmap, width, height, camera, frames, common, cam
             if i:
                 values = {key: keywords[key] for key in TerrainSession.REARMABLE if key in keywords}
                 mesh = (keywords["mesh_vertices"], keywords["mesh_indices"])
-                if dem_per_frame and not (keywords["exaggeration"] == held_dem[1] and np.array_equal(request.dem.view(np.uint32), held_dem[0].view(np.uint32))):  # (by bits: -0.0 is another DEM)
-                    session.reterrain(request.dem, request.camera, exaggeration=keywords["exaggeration"], **values)
-                    held_dem = (request.dem, keywords["exaggeration"])
-                elif mesh_per_frame and not (np.array_equal(mesh[0], held[0]) and np.array_equal(mesh[1], held[1])):
-                    # this frame's mesh (its own or common's) on the topology the session holds: a refit; else the create's path
+                dem = (request.dem, keywords["exaggeration"])
+                # which update frame i needs: the DEM (by bits: -0.0 is another DEM) or the exaggeration differs: a re-terrain;
+                # else the mesh differs: a re-mesh (equal indices: a refit on the topology the session holds, else the create's
+                # path); else a re-aim, or without per-frame cameras a re-arm
+                if update == "reterrain" and not (dem[1] == held_dem[1] and np.array_equal(dem[0].view(np.uint32), held_dem[0].view(np.uint32))):
+                    session.reterrain(dem[0], request.camera, exaggeration=dem[1], **values)
+                    held_dem = dem
+                elif update == "remesh" and not (np.array_equal(mesh[0], held[0]) and np.array_equal(mesh[1], held[1])):
                     session.remesh(mesh[0], None if np.array_equal(mesh[1], held[1]) else mesh[1], request.camera, **values)
                     held = mesh
-                elif mesh_per_frame or camera_per_frame or dem_per_frame:
-                    session.reaim(request.camera, **values)
-                else:
+                elif update == "rearm":
                     session.rearm(**values)
+                else:
+                    session.reaim(request.camera, **values)
             yield _with_sun(session.render(), sun)
     finally:
         session.close()

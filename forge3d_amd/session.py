@@ -108,8 +108,7 @@ class TerrainSession:
         given = dict(locals())
         given.pop("self")
         r = self._rearm_desc(given)
-        self._check(self._lib.f3d_session_rearm(self._handle, C.byref(r), self._err, len(self._err)))
-        self._note_armed(r)
+        self._update(self._lib.f3d_session_rearm, r, r)
 
     def reaim(self, camera=None, **rearmable):
         """rearm() under a new camera: what ``TerrainSession(..., camera=camera, **values)`` renders, on this session.
@@ -119,13 +118,9 @@ class TerrainSession:
         clears the per-render state; same contract as rearm().  Without a camera this is rearm()."""
         if camera is None:
             return self.rearm(**rearmable)
-        unknown = [k for k in rearmable if k not in self.REARMABLE]
-        if unknown:
-            raise TypeError(f"reaim() got an unexpected keyword argument {unknown[0]!r}")
-        a = self._reaim_desc(camera, rearmable)
-        self._check(self._lib.f3d_session_reaim(self._handle, C.byref(a), self._err, len(self._err)))
-        self._note_armed(a.arm)
-        self._camera = dict(camera)
+        self._known("reaim", rearmable)
+        a = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_reaim, a, a.arm, camera)
 
     def remesh(self, mesh_vertices, mesh_indices=None, camera=None, **rearmable):
         """reaim() under a moved or another mesh: what ``TerrainSession(..., mesh_vertices=..., mesh_indices=..., camera=camera,
@@ -135,30 +130,20 @@ class TerrainSession:
         ``mesh_indices`` (the same ones for a fresh tree, or another mesh) the create's path runs.  ``camera`` None keeps the
         current one (and the current exposure); otherwise it is read as reaim() reads it.  Same contract as reaim(): a
         refused value leaves the session as it was, rendering the old mesh."""
-        unknown = [k for k in rearmable if k not in self.REARMABLE]
-        if unknown:
-            raise TypeError(f"remesh() got an unexpected keyword argument {unknown[0]!r}")
+        self._known("remesh", rearmable)
         mv = np.ascontiguousarray(mesh_vertices, dtype=np.float32)
         if mv.ndim != 2 or mv.shape[1] != 3:
             raise ValueError("mesh_vertices must have shape (N, 3)")
         m = _native.RemeshDesc()
         m.struct_size = C.sizeof(_native.RemeshDesc)
         m.mesh_vertices, m.mesh_vertex_count = mv.ctypes.data, mv.shape[0]
-        mi = None
         if mesh_indices is not None:
             mi = np.ascontiguousarray(mesh_indices, dtype=np.uint32)
             if mi.ndim != 2 or mi.shape[1] != 3:
                 raise ValueError("mesh_indices must have shape (M, 3)")
             m.mesh_indices, m.mesh_index_count = mi.ctypes.data, mi.size
-        if camera is None:
-            m.aim = self._reaim_desc(self._camera, dict(rearmable, exposure=rearmable.get("exposure", self._armed["exposure"])))
-        else:
-            m.aim = self._reaim_desc(camera, rearmable)
-        self._check(self._lib.f3d_session_remesh(self._handle, C.byref(m), self._err, len(self._err)))
-        del mv, mi
-        self._note_armed(m.aim.arm)
-        if camera is not None:
-            self._camera = dict(camera)
+        m.aim = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_remesh, m, m.aim.arm, camera)  # (mv and mi live until here)
 
     def reterrain(self, heightmap, camera=None, *, at=None, exaggeration=None, **rearmable):
         """reaim() under new DEM samples: what ``TerrainSession(resulting_dem, ..., camera=camera, exaggeration=..., **values)``
@@ -169,9 +154,7 @@ class TerrainSession:
         value rescales every sample and needs the whole DEM.  ``camera`` None keeps the current one (and the current
         exposure); otherwise it is read as reaim() reads it.  DEM size and spacing stay the session's.  Same contract as
         reaim(): a refused value leaves the session as it was, rendering the old terrain."""
-        unknown = [k for k in rearmable if k not in self.REARMABLE]
-        if unknown:
-            raise TypeError(f"reterrain() got an unexpected keyword argument {unknown[0]!r}")
+        self._known("reterrain", rearmable)
         block = np.ascontiguousarray(heightmap, dtype=np.float32)
         if block.ndim != 2:
             raise ValueError(f"heightmap must be 2D (H, W), got shape {block.shape}")
@@ -192,13 +175,25 @@ class TerrainSession:
         t.exaggeration = 0.0 if exaggeration is None else float(exaggeration)
         if exaggeration is not None and float(exaggeration) == 0.0:
             t.exaggeration = float("nan")  # (0 means "keep" in the C ABI; a zero exaggeration is the create's refusal)
+        t.aim = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_reterrain, t, t.aim.arm, camera)  # (block lives until here)
+
+    # what the four updates share: the keyword check, the camera rule, the call with what the wrapper remembers of it
+    def _known(self, method: str, rearmable: dict) -> None:
+        unknown = [k for k in rearmable if k not in self.REARMABLE]
+        if unknown:
+            raise TypeError(f"{method}() got an unexpected keyword argument {unknown[0]!r}")
+
+    def _aim(self, camera, rearmable: dict) -> "_native.ReaimDesc":
+        """f3d_session_reaim_desc of an update: ``camera`` as the constructor reads it, or (None) the session's camera and
+        current exposure unless ``exposure=`` is given."""
         if camera is None:
-            t.aim = self._reaim_desc(self._camera, dict(rearmable, exposure=rearmable.get("exposure", self._armed["exposure"])))
-        else:
-            t.aim = self._reaim_desc(camera, rearmable)
-        self._check(self._lib.f3d_session_reterrain(self._handle, C.byref(t), self._err, len(self._err)))
-        del block
-        self._note_armed(t.aim.arm)
+            return self._reaim_desc(self._camera, dict(rearmable, exposure=rearmable.get("exposure", self._armed["exposure"])))
+        return self._reaim_desc(camera, rearmable)
+
+    def _update(self, entry, desc, arm, camera=None) -> None:
+        self._check(entry(self._handle, C.byref(desc), self._err, len(self._err)))
+        self._note_armed(arm)
         if camera is not None:
             self._camera = dict(camera)
 

@@ -21,6 +21,19 @@ _LIB = _HERE / "libf3d_emul.so"
 _CSRC = _HERE.parent.parent / "forge3d_amd" / "csrc"
 
 
+# what the emulator and every host harness that includes it are compiled with
+CXX = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off", "-DF3D_HORIZON_LAZY"]
+
+
+def build_harness(source: Path, name: str) -> C.CDLL:
+    """A host harness (tests/*_host/*.cpp: the emulator plus its own entry points) built in a fresh directory and loaded."""
+    import tempfile
+
+    out = Path(tempfile.mkdtemp(prefix=f"f3d_{name}_")) / f"lib{name}.so"
+    subprocess.run([*CXX, str(source), "-o", str(out)], check=True, capture_output=True)
+    return C.CDLL(str(out))
+
+
 def build(force=False):
     global _LIB
     srcs = [_HERE / "f3d_emul.cpp"] + sorted(_CSRC.glob("*.h"))
@@ -30,9 +43,7 @@ def build(force=False):
         _LIB = _HERE / ("libf3d_emul_%s.so" % hashlib.sha256(" ".join(extra).encode()).hexdigest()[:10])
     if force or not _LIB.exists() or _LIB.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
         tmp = _LIB.with_suffix(f".{os.getpid()}.tmp")  # parallel test workers may all find the library stale: build aside, then rename
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3",
-                        "-ffp-contract=off", "-DF3D_HORIZON_LAZY", *extra, str(_HERE / "f3d_emul.cpp"), "-o", str(tmp)],
-                       check=True, capture_output=True)
+        subprocess.run([*CXX, *extra, str(_HERE / "f3d_emul.cpp"), "-o", str(tmp)], check=True, capture_output=True)
         os.replace(tmp, _LIB)
     return _LIB
 

@@ -4,49 +4,9 @@
 // sun-ray certificates that the G-buffer pass writes under sun B, bit for bit.  The product's headers through the
 // emulator's scene set-up (host-built tables and mesh BVHs), one "lane" at a time.
 #include "../emul/f3d_emul.cpp"
+#include "../emul/host_scene.h"
 
 namespace {
-struct HostScene {
-    FrameParams P{};
-    HostTables t;
-    std::vector<float> mesh4;
-    MeshBvh bvh;
-    std::vector<Bvh4Node> bvh4;
-};
-
-// the scene of a descriptor as the emulator's render sets it up; mesh_form 1 = binary BVH walk, 2 = four wide
-void setup(HostScene &S, const f3d_terrain_ref_desc *d, int mesh_form) {
-    validate_desc(*d);
-    validate_scene(*d);
-    FrameParams &P = S.P;
-    (void)fill_uniforms(*d, P);
-    S.t = build_tables_host(d->heights, d->dem_width, d->dem_height, d->exaggeration);
-    S.t.attach(P.terrain);
-    S.t.attach_horizon(P.terrain);
-    if (d->mesh_vertices) {
-        S.mesh4 = pad_rgb_to_rgba(d->mesh_vertices, d->mesh_vertex_count, 0.0f);
-        P.mesh.vertices = (const float4 *)S.mesh4.data();
-        P.mesh.indices = d->mesh_indices;
-        P.mesh.vertex_count = d->mesh_vertex_count;
-        P.mesh.index_count = d->mesh_index_count;
-        P.mesh.traversal_mode = 0u;
-        S.bvh = build_mesh_bvh(d->mesh_vertices, d->mesh_vertex_count, d->mesh_indices, d->mesh_index_count);
-        P.mesh.bvh_nodes = S.bvh.nodes.data();
-        P.mesh.bvh_tris = (const float4 *)S.bvh.tris.data();
-        P.mesh.bvh_node_count = (uint32_t)S.bvh.nodes.size();
-        if (mesh_form == 2) {
-            S.bvh4 = collapse_bvh4(S.bvh);
-            if (!S.bvh4.empty()) {
-                P.mesh.bvh4_nodes = S.bvh4.data();
-                P.mesh.bvh4_node_count = (uint32_t)S.bvh4.size();
-            }
-            S.t.attach_mesh_grid(P.terrain, d->mesh_vertices, d->mesh_vertex_count, d->mesh_indices, d->mesh_index_count);
-        }
-    }
-    P.row_begin = 0u;
-    P.row_end = d->height;
-}
-
 void gbuffer(const FrameParams &P, std::vector<float4> &gbuf, std::vector<float> &dep, std::vector<float2> &sun) {
     const uint32_t W = P.cam.width, H = P.row_end - P.row_begin;
     gbuf.assign((size_t)W * H, float4{0.0f, 0.0f, 0.0f, 0.0f});
@@ -70,8 +30,8 @@ void gbuffer(const FrameParams &P, std::vector<float4> &gbuf, std::vector<float>
 extern "C" int rearm_check(const f3d_terrain_ref_desc *a, const f3d_terrain_ref_desc *b, int32_t mesh_form, uint64_t *out) {
     try {
         HostScene SA, SB;
-        setup(SA, a, mesh_form);
-        setup(SB, b, mesh_form);
+        setup(SA, a, mesh_form, 0u, 0u);
+        setup(SB, b, mesh_form, 0u, 0u);
         std::vector<float4> gbuf_a, gbuf_b;
         std::vector<float> dep_a, dep_b;
         std::vector<float2> sun_a, sun_b;

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import scenes
+from emul import emul
 from test_session_rearm_host import _desc, _no_device, _wrapper_error
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -33,11 +34,7 @@ KINDS = ("other", "same", "fov", "up", "sky", "below", "nadir")
 
 @pytest.fixture(scope="module")
 def harness():
-    out = Path(tempfile.mkdtemp(prefix="f3d_reaim_host_")) / "libreaim_host.so"
-    # (the emulator's flags, tests/emul/emul.py)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
-                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
-    lib = C.CDLL(str(out))
+    lib = emul.build_harness(HARNESS, "reaim_host")
     lib.reaim_check.restype = C.c_int
     lib.reaim_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32,
                                 C.POINTER(C.c_uint64)]

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import scenes
+from emul import emul
 
 ROOT = Path(__file__).resolve().parent.parent
 HARNESS = ROOT / "tests" / "rearm_host" / "rearm_harness.cpp"
@@ -29,11 +30,7 @@ SCENES = 240
 
 @pytest.fixture(scope="module")
 def harness():
-    out = Path(tempfile.mkdtemp(prefix="f3d_rearm_host_")) / "librearm_host.so"
-    # (the emulator's flags, tests/emul/emul.py)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
-                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
-    lib = C.CDLL(str(out))
+    lib = emul.build_harness(HARNESS, "rearm_host")
     lib.rearm_check.restype = C.c_int
     return lib
 

@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import scenes
+from emul import emul
 from test_session_rearm_host import _no_device, _wrapper_error
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -40,11 +41,7 @@ FIELDS = ("leaf_boxes", "parent_boxes", "empty_slots", "topology", "triangles", 
 
 @pytest.fixture(scope="module")
 def harness():
-    out = Path(tempfile.mkdtemp(prefix="f3d_remesh_host_")) / "libremesh_host.so"
-    # (the emulator's flags, tests/emul/emul.py)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
-                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
-    lib = C.CDLL(str(out))
+    lib = emul.build_harness(HARNESS, "remesh_host")
     lib.remesh_check.restype = C.c_int
     lib.remesh_check.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                  C.c_uint64, C.POINTER(C.c_uint64)]

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import scenes
+from emul import emul
 from test_session_rearm_host import _no_device, _wrapper_error
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -35,11 +36,7 @@ FIELDS = ("leaf", "band", "outside", "compared", "dirty_cells", "tiles")
 
 @pytest.fixture(scope="module")
 def harness():
-    out = Path(tempfile.mkdtemp(prefix="f3d_reterrain_host_")) / "libreterrain_host.so"
-    # (the emulator's flags, tests/emul/emul.py)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-64-v3", "-ffp-contract=off",
-                    "-DF3D_HORIZON_LAZY", str(HARNESS), "-o", str(out)], check=True, capture_output=True)
-    lib = C.CDLL(str(out))
+    lib = emul.build_harness(HARNESS, "reterrain_host")
     lib.reterrain_chain.restype = C.c_int
     lib.reterrain_chain.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.c_void_p]
