@@ -146,6 +146,21 @@ class ReterrainDesc(C.Structure):
     ]
 
 
+class QueryDesc(C.Structure):
+    """f3d_session_query_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("mode", C.c_uint32), ("flags", C.c_uint32), ("count", C.c_uint32),
+        ("rays", C.c_void_p),
+        ("kind", C.c_void_p), ("t", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p),
+        ("primitive", C.c_void_p), ("direction", C.c_void_p),
+    ]
+
+
+QUERY_CLOSEST, QUERY_OCCLUSION, QUERY_PIXELS = 0, 1, 2
+QUERY_TERRAIN_ONLY, QUERY_CURVED, QUERY_DEVICE_POINTERS, QUERY_NO_WAIT = 1, 2, 4, 8
+QUERY_SCRATCH_BYTES_PER_RAY = 80  # F3D_QUERY_SCRATCH_BYTES_PER_RAY
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -183,6 +198,7 @@ ABI = [
     ("f3d_session_reaim", C.c_int, [C.c_void_p, _P(ReaimDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_remesh", C.c_int, [C.c_void_p, _P(RemeshDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_reterrain", C.c_int, [C.c_void_p, _P(ReterrainDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_query", C.c_int, [C.c_void_p, _P(QueryDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
     ("f3d_session_halo", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p), _P(C.c_uint64)]),

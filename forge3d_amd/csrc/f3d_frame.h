@@ -12,6 +12,7 @@
 #pragma once
 #include "f3d_launch.h"
 #include "f3d_shade.h"
+#include "f3d_query.h"
 #include "f3d_lds.h"
 
 namespace f3d {
@@ -781,6 +782,17 @@ __global__ __launch_bounds__(kWave) void k_ray_batch(const RayBatchParams B) {
         B.out_normal[3 * i + 1] = h.hit ? h.n.y : 0.0f;
         B.out_normal[3 * i + 2] = h.hit ? h.n.z : 0.0f;
     }
+}
+
+// Ray queries on a live session (f3d_session_query; f3d_query.h query_lane): one lane a ray, one wave a workgroup, the
+// wave's LdsPending rows -- k_ray_batch's shape over the session's whole scene.  MESH as for k_frame: terrain-only scenes and
+// TERRAIN_ONLY queries run the instantiation without the mesh walk.
+template <bool MESH>
+__global__ __launch_bounds__(kWave) void k_query(const QueryParams Q) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+    typename PendingFor<MESH>::type pend{make_pending(lds, Q.frame.terrain)};
+    const uint32_t i = blockIdx.x * kWave + threadIdx.x;
+    if (i < Q.count) query_lane(Q, i, pend);
 }
 
 // ---- acceleration-table builders (reference build_minmax_mips,

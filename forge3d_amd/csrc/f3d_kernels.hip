@@ -204,6 +204,13 @@ hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(k_ray_batch, dim3((p.n + kWave - 1) / kWave), dim3(kWave), 0, stream, p);
     return hipGetLastError();
 }
+hipError_t launch_query(const QueryParams &p, hipStream_t stream) {
+    if (p.count == 0u) return hipSuccess;
+    const dim3 grid((p.count + kWave - 1u) / kWave), block(kWave);
+    if (p.frame.mesh.traversal_mode == 0u) hipLaunchKernelGGL((k_query<true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_query<false>), grid, block, 0, stream, p);
+    return hipGetLastError();
+}
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream) {
     dim3 block(16, 16), grid((p.leaf_dim_x + 15) / 16, (p.leaf_dim_y + 15) / 16);
     hipLaunchKernelGGL(k_leaf_build, grid, block, 0, stream, p);

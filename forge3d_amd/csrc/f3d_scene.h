@@ -245,4 +245,22 @@ struct RearmParams {
     uint32_t tiles;           // entries of tile_cost
 };
 
+// Ray queries on a live session (f3d_session_query; k_query, f3d_query.h): frame = the session's uniforms as the frames
+// read them (TERRAIN_ONLY: mesh.traversal_mode = 3), one lane a ray.  Every output may be null.
+constexpr uint32_t kQueryClosest = 0u, kQueryOccluded = 1u, kQueryPixels = 2u;
+struct QueryParams {
+    FrameParams frame;
+    uint32_t mode;           // kQuery*
+    uint32_t curved;         // mode 1: the sun rays' curvature policy
+    uint32_t count;
+    const float4 *rays;      // modes 0 / 1: 2 float4 per ray: (origin, tmin), (direction, tmax)
+    const uint2 *pixels;     // mode 2: (gx, gy), full-image coordinates
+    uint32_t *kind;          // 0 miss, 1 terrain, 2 mesh; mode 1: 0 clear / 1 occluded
+    float *t;                // qNaN 0x7fc00000 on a miss
+    float *normal;           // 3 per ray, zeros on a miss
+    float *position;         // 3 per ray, zeros on a miss
+    uint32_t *primitive;     // terrain: cx | cz << 16; mesh: triangle index; miss: 0xFFFFFFFF
+    float *direction;        // mode 2: 3 per ray, the centre ray's direction
+};
+
 }  // namespace f3d

@@ -29,7 +29,9 @@ struct SurfaceHit {
 
 // intersect_mesh, hybrid_traversal.wgsl:137-172: the reference sweeps every triangle
 // (its BVH buffer is bound but never read); triangle data is wave-uniform here.
-F3D_HD bool mesh_sweep(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best) {
+// tri_out (every walker below; the ray queries' `primitive`, f3d_query.h): the winning triangle's index in the caller's
+// mesh_indices -- the loop index here, v0.w of the leaf-order triangles in the tree walks; untouched without a hit
+F3D_HD bool mesh_sweep(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best, uint32_t *tri_out = nullptr) {
     bool any = false;
     t_best = tmax;
     if (M.index_count < 3u) return false;
@@ -44,6 +46,7 @@ F3D_HD bool mesh_sweep(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, flo
             t_best = t;
             n_best = n;
             any = true;
+            if (tri_out) *tri_out = tri / 3u;
         }
     }
     return any;
@@ -81,7 +84,7 @@ extern unsigned long long g_host_mesh_stats[8];
 // best_tri, not in a boolean carried through the regions; an occlusion ray that has its answer leaves by setting node past
 // the end.
 template <bool ANY>
-F3D_HD bool mesh_bvh(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best) {
+F3D_HD bool mesh_bvh(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best, uint32_t *tri_out = nullptr) {
     const float ix = (d.x < 0.0f ? -1.0f : 1.0f) / f_max(f_abs(d.x), 1e-12f);
     const float iy = (d.y < 0.0f ? -1.0f : 1.0f) / f_max(f_abs(d.y), 1e-12f);
     const float iz = (d.z < 0.0f ? -1.0f : 1.0f) / f_max(f_abs(d.z), 1e-12f);
@@ -133,6 +136,7 @@ F3D_HD bool mesh_bvh(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float
         node = next;
     }
     any = best_tri != 0xFFFFFFFFu;
+    if (tri_out && any) *tri_out = best_tri;
     return any;
 }
 
@@ -148,7 +152,7 @@ F3D_HD bool mesh_bvh(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float
 // configs[3] stand-in, 4 001 / 4 010 -> 4 116 / 4 114 Msamples/s; -DF3D_BVH4_SLOT_ORDER is the slot-order walk it replaced,
 // whose level word was (first_child << 4) | mask of the inner slots still to visit).
 template <bool ANY, class Stack>
-F3D_HD bool mesh_bvh4(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best, Stack &stk) {
+F3D_HD bool mesh_bvh4(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best, Stack &stk, uint32_t *tri_out = nullptr) {
     const float ix = (d.x < 0.0f ? -1.0f : 1.0f) / f_max(f_abs(d.x), 1e-12f);
     const float iy = (d.y < 0.0f ? -1.0f : 1.0f) / f_max(f_abs(d.y), 1e-12f);
     const float iz = (d.z < 0.0f ? -1.0f : 1.0f) / f_max(f_abs(d.z), 1e-12f);
@@ -277,14 +281,15 @@ F3D_HD bool mesh_bvh4(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, floa
         }
         node = next;
     }
+    if (tri_out && best_tri != 0xFFFFFFFFu) *tri_out = best_tri;
     return best_tri != 0xFFFFFFFFu;
 }
 
 template <class Stack>
-F3D_HD bool mesh_closest(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best, Stack &stk) {
-    if (M.bvh4_nodes) return mesh_bvh4<false>(M, o, tmin, d, tmax, t_best, n_best, stk);
-    if (M.bvh_nodes) return mesh_bvh<false>(M, o, tmin, d, tmax, t_best, n_best);
-    return mesh_sweep(M, o, tmin, d, tmax, t_best, n_best);
+F3D_HD bool mesh_closest(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float &t_best, V3 &n_best, Stack &stk, uint32_t *tri_out = nullptr) {
+    if (M.bvh4_nodes) return mesh_bvh4<false>(M, o, tmin, d, tmax, t_best, n_best, stk, tri_out);
+    if (M.bvh_nodes) return mesh_bvh<false>(M, o, tmin, d, tmax, t_best, n_best, tri_out);
+    return mesh_sweep(M, o, tmin, d, tmax, t_best, n_best, tri_out);
 }
 // Is any triangle of the mesh hit (occlusion rays)?
 template <class Stack>
@@ -296,9 +301,11 @@ F3D_HD bool mesh_any(const MeshDev &M, V3 o, float tmin, V3 d, float tmax, float
 
 // intersect_hybrid, hybrid_traversal.wgsl:175-201 (closest hit, curvature off)
 // t_clear / level: a certificate for camera rays (f3d_cone.h); t_clear = 0 starts the march at the root.
+// primitive (the ray queries, f3d_query.h; the frame kernels pass none): what was hit -- the terrain cell cx | cz << 16, or the
+// mesh triangle's index in the caller's mesh_indices; untouched on a miss.
 template <class Pending>
 F3D_HD SurfaceHit closest_hit(const FrameParams &P, V3 o, float tmin, V3 d, float tmax, Pending &pend, float t_clear = 0.0f,
-                              uint32_t start_level = 0u) {
+                              uint32_t start_level = 0u, uint32_t *primitive = nullptr) {
     SurfaceHit best;
     best.kind = 0u;
     best.t = tmax;
@@ -354,7 +361,7 @@ F3D_HD SurfaceHit closest_hit(const FrameParams &P, V3 o, float tmin, V3 d, floa
 #endif
         float t;
         V3 n;
-        if (mesh_closest(P.mesh, o, tmin, d, tmax, t, n, pend) && t < best.t) {
+        if (mesh_closest(P.mesh, o, tmin, d, tmax, t, n, pend, primitive) && t < best.t) {
             best.kind = 2u;
             best.t = t;
             best.n = n;
@@ -366,13 +373,18 @@ F3D_HD SurfaceHit closest_hit(const FrameParams &P, V3 o, float tmin, V3 d, floa
     TraceHit th = trace_terrain(P.terrain, r, false, pend);  // the reference-shaped sorted descent
 #else
     // camera rays enter the footprint from outside: the march starts at the root, or where the pixel's certificate ends
-    TraceHit th = march_terrain_from<false, false>(P.terrain, r, false, march_begin_at(P.terrain, r, t_clear, start_level), pend);
+    uint32_t cell = 0u;
+    TraceHit th = march_terrain_from<false, false>(P.terrain, r, false, march_begin_at(P.terrain, r, t_clear, start_level), pend, 3.0e38f,
+                                                   primitive ? &cell : nullptr);
 #endif
     if (th.hit && th.t < best.t) {
         best.kind = 1u;
         best.t = th.t;
         best.n = th.n;
         best.p = along(o, th.t, d);
+#if !defined(F3D_TRAVERSAL_DESCENT)
+        if (primitive) *primitive = cell;
+#endif
     }
     return best;
 }

@@ -29,7 +29,7 @@ class ViewerError(Exception):
 _RASTER_ONLY = ("load_obj", "load_gltf", "load_bundle", "load_overlay", "load_point_cloud", "set_point_cloud_params",
                 "set_transform", "add_label", "add_labels", "add_line_label", "add_curved_label", "add_callout",
                 "add_vector_overlay", "set_labels_enabled", "clear_labels", "remove_label", "set_label_typography",
-                "set_declutter_algorithm", "poll_pick_events", "pick_at", "update_labels", "load_label_atlas",
+                "set_declutter_algorithm", "poll_pick_events", "update_labels", "load_label_atlas",
                 "set_terrain_scatter", "clear_terrain_scatter", "apply_scene_variant", "set_review_layer_visible")
 
 
@@ -118,6 +118,27 @@ class ViewerHandle(OfflineTerrainViewer):
             _io.numpy_to_png(out / f"frame_{i:04d}.png", result["rgba"])
             if progress_callback:
                 progress_callback(i, len(animation))
+
+    def pick_at(self, x: int, y: int, *, shift: bool = False, ctrl: bool = False) -> list:
+        """What lies under pixel (x, y) of the viewer's current scene and camera (reference viewer.py:910): one closest-hit
+        ray through the pixel's centre on a session of that scene (TerrainSession.pick) -- ``[{"kind": "terrain" | "mesh",
+        "world_pos": [x, y, z], "distance": t, "normal": [...], "primitive": int}]``, or ``[]`` for sky.  ``shift`` / ``ctrl``
+        (the raster viewer's selection modifiers) are accepted and ignored.  Parity with the reference is NOT pinned: its
+        pick reads the frozen frame of its raster viewer (feature ids, f64 viewer-world positions); this one is the path
+        tracer's own centre ray, exact for what the path tracer renders."""
+        from .session import TerrainSession
+
+        _ = shift, ctrl
+        dem, w, h, camera, keywords = self._call()
+        if not (0 <= int(x) < w and 0 <= int(y) < h):
+            raise ViewerError(f"pick_at({x}, {y}) is outside the {w}x{h} viewport")
+        with TerrainSession(dem, w, h, camera, **keywords) as s:
+            hit = s.pick(np.array([[int(x), int(y)]], np.uint32))
+        kind = int(hit["kind"][0])
+        if kind == 0:
+            return []
+        return [{"kind": "terrain" if kind == 1 else "mesh", "world_pos": [float(v) for v in hit["position"][0]],
+                 "distance": float(hit["t"][0]), "normal": [float(v) for v in hit["normal"][0]], "primitive": int(hit["primitive"][0])}]
 
     def get_stats(self) -> Dict[str, Any]:
         last = self.last_result or {}

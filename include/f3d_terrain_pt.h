@@ -422,6 +422,57 @@ typedef struct f3d_session_reterrain_desc {
     f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
 } f3d_session_reterrain_desc;
 int f3d_session_reterrain(f3d_session *session, const f3d_session_reterrain_desc *desc, char *err, size_t errlen);
+/* ---- ray queries: pick, line of sight, ground --------------------------------------------------------------------------
+ * A live session holds the only current copy of its scene -- the ground after a re-terrain (no raw-height copy of the DEM is
+ * kept), the mesh after a re-mesh, the camera after a re-aim.  A query asks that scene a question with the frame kernels' own
+ * device functions, one lane a ray (k_query, csrc/f3d_query.h), and changes nothing a frame launch reads: it is allowed at
+ * any time, between frames and on sessions with connected peer halos.
+ *   mode 0  closest hit  the caller's ray as given -> the reference's intersect_hybrid (curvature off, mesh and terrain)
+ *   mode 1  occlusion    the caller's ray as given -> the any-hit march of the shadow / IBL rays; CURVED: with the sun rays'
+ *                        curvature policy.  Answers `kind` only (any other output: refused, status 1): an any-hit walk stops
+ *                        at the first surface it meets, its t is not the closest hit's
+ *   mode 2  pixels       the centre ray of pixel (gx, gy) of the session's CURRENT camera (origin = camera, tmin 1e-3, tmax 1e30):
+ *                        the bits the G-buffer pass stores in the depth and normal AOVs.  Full-image coordinates: a strip session
+ *                        answers for any pixel of the image.  A pixel outside the image: refused (status 1) before anything
+ *                        is enqueued (DEVICE_POINTERS: its lane answers a miss -- the host never sees the pixels)
+ * In modes 0 and 1 t is in units of |direction|: nothing is normalised.  Answers do not depend on the form of the mesh's tree.
+ * TERRAIN_ONLY leaves the mesh out ("clamp to ground": an object must not land on itself).
+ * A BAD ray -- a non-finite component, a direction whose squared length is not a positive finite f32, tmax <= tmin -- is
+ * never refused and never marched: its lane answers a miss before any walk starts, in the host and the device form alike.
+ * Ordering: the kernel is enqueued on the session stream behind everything enqueued so far (band streams included), as a
+ * re-arm is: a query right after a re-aim / re-mesh / re-terrain sees the new scene, no host wait in between.
+ *   host pointers (default)  blocking.  Rays go up and results come down through the library's pinned staging pair in stream
+ *       order (no plain copy races frames in flight), via a scratch buffer of the session: 80 bytes a ray (32 in, 48 out,
+ *       whichever outputs are asked for), allocated when a larger count than any before arrives -- against
+ *       memory_budget_bytes (too small: status 2, session unchanged) and counted in gpu_resource_bytes
+ *   DEVICE_POINTERS          rays and every output are device memory (rays 16-byte aligned); nothing is copied or allocated.
+ *       The call returns when the kernel has finished, or -- NO_WAIT -- with it in flight: the caller orders by the stream
+ *       the session was created on
+ * count == 0 is a successful no-op.  No ABI version bump: detected by the symbol f3d_session_query. */
+#define F3D_QUERY_CLOSEST 0u
+#define F3D_QUERY_OCCLUSION 1u
+#define F3D_QUERY_PIXELS 2u
+#define F3D_QUERY_TERRAIN_ONLY 1u
+#define F3D_QUERY_CURVED 2u
+#define F3D_QUERY_DEVICE_POINTERS 4u
+#define F3D_QUERY_NO_WAIT 8u
+#define F3D_QUERY_SCRATCH_BYTES_PER_RAY 80u
+typedef struct f3d_session_query_desc {
+    uint32_t struct_size; /* = sizeof(f3d_session_query_desc) of the caller's header */
+    uint32_t mode;        /* F3D_QUERY_CLOSEST / _OCCLUSION / _PIXELS */
+    uint32_t flags;       /* F3D_QUERY_TERRAIN_ONLY | _CURVED (mode 1 only) | _DEVICE_POINTERS | _NO_WAIT (with _DEVICE_POINTERS only) */
+    uint32_t count;
+    const void *rays;     /* modes 0 / 1: count x 8 f32 (origin xyz, tmin, direction xyz, tmax) -- the layout of f3d_terrain_trace_batch;
+                             mode 2: count x 2 u32 (gx, gy), full-image coordinates */
+    /* outputs, each may be NULL */
+    uint32_t *kind;       /* 0 miss, 1 terrain, 2 mesh; mode 1: 0 clear / 1 occluded */
+    float *t;             /* ray parameter; qNaN 0x7fc00000 on a miss (what the depth AOV holds) */
+    float *normal;        /* count x 3; zeros on a miss */
+    float *position;      /* count x 3: origin + t * direction as closest_hit forms it; zeros on a miss */
+    uint32_t *primitive;  /* terrain: cx | cz << 16 of the hit cell; mesh: the triangle's index in the caller's mesh_indices; miss: 0xFFFFFFFF */
+    float *direction;     /* count x 3, mode 2 only: the centre ray's direction */
+} f3d_session_query_desc;
+int f3d_session_query(f3d_session *session, const f3d_session_query_desc *desc, char *err, size_t errlen);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);
