@@ -15,6 +15,9 @@
 #ifndef F3D_HORIZON_THETA
 #define F3D_HORIZON_THETA 8.0f  // a node is taken whole when it is this many times smaller than its distance (A/B: 4, 6)
 #endif
+#if !defined(__HIPCC__)
+#include <cstdlib>  // getenv: sky_shortcut_enabled
+#endif
 
 // (included by f3d_shade.h after camera_dir, which it uses)
 
@@ -22,7 +25,7 @@ namespace f3d {
 
 struct PrimaryStart {
     float t_clear;   // 0: no certificate (march from the root); 3e38: no ray of the pixel ever meets terrain
-    uint32_t level;  // level of the node the certificate stopped at: where to drop the rays in
+    uint32_t level;  // level of the node the certificate stopped at: where to drop the rays in (| kSkyBeyond, below)
 };
 
 // Largest band maximum of the 3 x 3 nodes of `level` around (nx, nz) (nodes outside the grid hold no terrain).
@@ -35,6 +38,56 @@ F3D_HD float cone_max9(const TerrainDev &T, uint32_t level, uint32_t nx, uint32_
                 mx = f_max(mx, T.bands[T.band_offset[level] + (qz << T.band_shift[level]) + qx].mx);
         }
     return mx;
+}
+
+// A pixel none of whose camera rays meets terrain says so in one of two ways: t_clear = 3e38 (clear all the way), or a
+// finite t_clear -- clear up to there, as ever -- with kSkyBeyond set in the level word: "and no ray meets terrain beyond
+// it either" (the cone comes down again, but only after all of it has left the footprint: leaves_clear below).  A camera
+// ray of such a pixel is a miss without being formed (f3d_shade.h sample_primary), and a wave whose pixels all say so skips
+// its sample loop (f3d_frame.h frame_lanes).  A reader that does not ask takes the march's own way to the same miss
+// (f3d_march.h march_begin_at, with start_level).  (kSkyBeyond, start_level: f3d_scene.h, for the PBR tracer's reader too.)
+constexpr float kClearForever = 3.0e38f;
+F3D_HD bool certified_sky(uint2 start) { return f_from_bits(start.x) == kClearForever || (start.y & kSkyBeyond) != 0u; }
+
+// The tests' switch, in host-only builds of these headers (tests/emul) alone: with F3D_EMUL_NO_SKY_SHORTCUT set,
+// sample_primary marches the rays of certified pixels as it did before it knew of the certificate.  The device library has
+// no switch.
+#if defined(__HIPCC__)
+F3D_HD bool sky_shortcut_enabled() { return true; }
+#else
+inline bool sky_shortcut_enabled() { return getenv("F3D_EMUL_NO_SKY_SHORTCUT") == nullptr; }
+#endif
+
+// Does every ray of the cone (apex r.o, directions within `delta` of r.d) pass BESIDE the footprint: is its root interval
+// (f3d_march.h march_root_interval) empty?  In the x-z plane: a line through the apex with unit normal n has the footprint,
+// dilated by 2 m on every side, on its far side (n . v <= m / 2 for the four dilated corners v, seen from the apex -- so
+// n . v <= -3/2 m on the footprint itself), and every ray of the cone moves to the near side or along the line
+// (n . d' >= n . d - delta >= 0): no point of a ray, at any parameter > 0, is nearer than 3/2 m to the footprint.  The
+// lines tried are the eight through the apex and a dilated corner; the two tangents of the dilated footprint are among them.
+// m is 0.02 cells plus 1e-5 of the coordinates' size: a parameter inside the march's interval puts the ray within a few
+// ulp of those coordinates of the footprint (plane_at, the subtraction, inv_x / inv_z and the product round once each),
+// 30 times less than m.  The 1e-6 on delta covers the directions' own rounding and safe_inv's clamp of a zero component.
+F3D_HD bool cone_beside_footprint(const TerrainDev &T, const RayCtx &r, float delta) {
+    const float xa = plane_at(T.origin_x, 0u, T.spacing_x), xb = plane_at(T.origin_x, T.cell_w, T.spacing_x);
+    const float za = plane_at(T.origin_z, 0u, T.spacing_z), zb = plane_at(T.origin_z, T.cell_h, T.spacing_z);
+    const float scale = f_abs(r.o.x) + f_abs(r.o.z) + f_max(f_abs(xa), f_abs(xb)) + f_max(f_abs(za), f_abs(zb));
+    const float m = 0.02f * f_min(T.spacing_x, T.spacing_z) + 1e-5f * scale;
+    const float vx[2] = {f_min(xa, xb) - 2.0f * m - r.o.x, f_max(xa, xb) + 2.0f * m - r.o.x};
+    const float vz[2] = {f_min(za, zb) - 2.0f * m - r.o.z, f_max(za, zb) + 2.0f * m - r.o.z};
+    for (uint32_t k = 0u; k < 8u; k++) {
+        const float sign = (k & 4u) ? -1.0f : 1.0f;
+        float nx = -sign * vz[(k >> 1) & 1u], nz = sign * vx[k & 1u];
+        const float len2 = nx * nx + nz * nz;
+        if (!(len2 > 0.0f)) continue;
+        const float inv = 1.0f / f_sqrt(len2);
+        nx *= inv;
+        nz *= inv;
+        bool far_side = true;
+        for (uint32_t j = 0u; j < 4u; j++)
+            if (!(nx * vx[j & 1u] + nz * vz[j >> 1] <= 0.5f * m)) far_side = false;
+        if (far_side && nx * r.d.x + nz * r.d.z >= delta + 1e-6f) return true;
+    }
+    return false;
 }
 
 F3D_HD PrimaryStart primary_start(const FrameParams &P, uint32_t gx, uint32_t gy) {
@@ -51,7 +104,10 @@ F3D_HD PrimaryStart primary_start(const FrameParams &P, uint32_t gx, uint32_t gy
     const RayCtx r = make_ray(T, P.cam.origin, 1e-3f, d, 1e30f, false);
     float t_in, t_out;
     march_root_interval(T, r, t_in, t_out);
-    if (t_in > t_out) return out;  // the centre ray misses the footprint; its neighbours may not: no certificate
+    if (t_in > t_out) {  // the centre ray misses the footprint; its neighbours may not: certified only if the whole cone does
+        if (cone_beside_footprint(T, r, delta)) out.t_clear = kClearForever;
+        return out;
+    }
     const float cell = f_min(T.spacing_x, T.spacing_z);
     // height margin: the band test compares f32 heights of the order of the ray's and the terrain's
     const float y_scale = f_abs(r.o.y) + f_abs(T.bands[T.band_offset[top]].mx) + f_abs(T.bands[T.band_offset[top]].mn);
@@ -66,8 +122,28 @@ F3D_HD PrimaryStart primary_start(const FrameParams &P, uint32_t gx, uint32_t gy
         return r.d.y - delta >= 0.0f && lowest(b) > T.bands[T.band_offset[top]].mx;
     };
     const bool x_forward = !(r.d.x < 0.0f), z_forward = !(r.d.z < 0.0f);
+    // ... or it comes down, but only after all of it has left the footprint.  A ray of the cone moves towards the edge the
+    // centre ray leaves through by no less than |d| - delta per unit of t, so by the parameter `gone` every ray is beyond
+    // that edge, for good (margins as in cone_beside_footprint).  Between b and `gone` the cone is over cells no farther
+    // than `reach` from the centre ray's exit point -- in node (nx, nz) of `lvl`: the 3 x 3 block of nodes at least that
+    // wide around it holds them (at the top level: all cells), and the cone's lowest ray must clear the block's maximum.
+    auto leaves_clear = [&](float b, uint32_t lvl, uint32_t nx, uint32_t nz) F3D_LAMBDA {
+        const float xs = plane_at(T.origin_x, x_forward ? T.cell_w : 0u, T.spacing_x), zs = plane_at(T.origin_z, z_forward ? T.cell_h : 0u, T.spacing_z);
+        const float slack = 0.02f * cell + 1e-5f * (f_abs(r.o.x) + f_abs(r.o.z) + f_abs(xs) + f_abs(zs));
+        const float ax = f_abs(r.d.x) - delta - 1e-6f, az = f_abs(r.d.z) - delta - 1e-6f;
+        float gone = 3.0e38f;
+        if (ax > 0.0f) gone = f_min(gone, (f_abs(xs - r.o.x) + slack) / ax);
+        if (az > 0.0f) gone = f_min(gone, (f_abs(zs - r.o.z) + slack) / az);
+        if (!(gone < 1e30f)) return false;
+        gone = f_max(gone * 1.00001f, b);
+        const float reach = 1.01f * (gone - b) + gone * delta + 0.02f * cell;
+        uint32_t q = lvl;
+        while (q < top && cell * (float)(1u << q) < reach) q++;
+        return f_min(lowest(b), lowest(gone)) > cone_max9(T, q, nx >> (q - lvl), nz >> (q - lvl));
+    };
     uint32_t level = top, nx = 0u, nz = 0u;
     float clear = t_in;
+    bool beyond = false;  // clear up to `clear`, where the centre ray leaves the footprint, and nothing beyond it (leaves_clear)
     for (uint32_t iter = 0u; iter < 512u; iter++) {
         uint32_t cx1 = (nx + 1u) << level, cz1 = (nz + 1u) << level;
         cx1 = cx1 < T.cell_w ? cx1 : T.cell_w;
@@ -96,14 +172,16 @@ F3D_HD PrimaryStart primary_start(const FrameParams &P, uint32_t gx, uint32_t gy
         if (wide_enough && y_low > cone_max9(T, ql, nx >> (ql - level), nz >> (ql - level))) {
             clear = b;
             if (!(b < t_out)) {
-                if (beyond_is_clear(b)) clear = 3.0e38f;
+                if (beyond_is_clear(b)) clear = kClearForever;
+                else beyond = leaves_clear(b, level, nx, nz);
                 break;
             }
             const bool cross_x = x_out <= z_out, cross_z = z_out <= x_out;
             const uint32_t qx = nx + ((cross_x && x_forward) ? 1u : 0u) - ((cross_x && !x_forward) ? 1u : 0u);
             const uint32_t qz = nz + ((cross_z && z_forward) ? 1u : 0u) - ((cross_z && !z_forward) ? 1u : 0u);
             if ((qx << level) >= T.cell_w || (qz << level) >= T.cell_h) {
-                if (beyond_is_clear(b)) clear = 3.0e38f;
+                if (beyond_is_clear(b)) clear = kClearForever;
+                else beyond = leaves_clear(b, level, nx, nz);
                 break;
             }
             const bool up = level < top && (((qx ^ nx) | (qz ^ nz)) > 1u);
@@ -128,7 +206,7 @@ F3D_HD PrimaryStart primary_start(const FrameParams &P, uint32_t gx, uint32_t gy
         }
     }
     out.t_clear = clear > t_in ? clear : 0.0f;
-    out.level = level;
+    out.level = level | ((beyond && clear > t_in) ? kSkyBeyond : 0u);
     return out;
 }
 

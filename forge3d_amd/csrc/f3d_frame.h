@@ -193,19 +193,40 @@ __device__ __forceinline__ float frame_lanes(const FrameParams &P, uint32_t tile
     // accumulators of the samples so far (6 words) and the frame head's record (2 words).
     uint32_t *park = pend.col + kParkRow * kWave;
     uint32_t stream = 0u;  // state at the start of the current round
+    // A tile of sky: every pixel of the wave holds the certificate "no camera ray of mine meets terrain" (f3d_cone.h; lanes
+    // outside the image count as holding it), there is no mesh to walk and the environment is uniform.  All its samples are
+    // misses with one and the same contribution, so the wave parks the samples' sum (f3d_shade.h all_miss_radiance) around
+    // the empty candidate and goes to the tail: 60 % of the headline frame's pixels.  One load and one ballot for every
+    // wave; the word is dead after the ballot and the flag is wave-uniform.
+    bool sky_tile = false;
     {
         uint32_t gx, gy;
         lane_pixel<S>(P, tile, gx, gy);
         uint2 rec = uint2{f_bits(1.0f), 0u};  // no reuse, centre ray missed, no usable history
+        bool sky = true;
         if (valid) {
-            rec = P.head[(size_t)(gy - P.row_begin) * P.cam.width + gx];  // k_head
+            const size_t lp = (size_t)(gy - P.row_begin) * P.cam.width + gx;
+            rec = P.head[lp];  // k_head
             stream = P.cam.seed_hi ^ (gx * 1664525u) ^ (gy * 1013904223u) ^ (P.frame_index * 92837111u) ^ P.cam.seed_lo;
+#if !defined(F3D_NO_PRIMARY_START)  // A/B builds (tools/build_variant.sh)
+            sky = P.primary_start != nullptr && certified_sky(P.primary_start[lp]);
+#else
+            sky = false;
+#endif
         }
         park[kParkHead * kWave] = rec.x;
         park[(kParkHead + 1) * kWave] = rec.y;
+        sky_tile = __ballot(!sky) == 0ull && env_is_uniform(P.env) && !(Pending::kMesh && P.mesh.traversal_mode == 0u);
     }
 #pragma unroll
     for (int w = 0; w < kParkHead; w++) park[w * kWave] = 0u;  // radiance = 0, empty candidate reservoir
+    if (sky_tile) {
+        const V3 radiance = all_miss_radiance(P);
+        park[0] = f_bits(radiance.x);
+        park[kWave] = f_bits(radiance.y);
+        park[2 * kWave] = f_bits(radiance.z);
+    }
+    if (!sky_tile)  // (a branch around the loop, not a bound of it: nothing new is live across the marches)
     for (uint32_t s0 = 0u; s0 < P.spp; s0 += S) {  // wave-uniform
         const uint32_t n_act = P.spp - s0 < S ? P.spp - s0 : S;
         const bool act = valid && (lane_now() & (S - 1u)) < n_act;

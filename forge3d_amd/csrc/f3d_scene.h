@@ -172,6 +172,10 @@ struct alignas(16) PackedReservoir {
     float target_pdf;
 };
 constexpr uint32_t kLightTypeBit = 0x80000000u;
+// Primary-ray certificate records {t_clear bits, level} (f3d_cone.h): bit 31 of the level word says "and no ray of the pixel
+// meets terrain beyond t_clear either" (levels are < 32).
+constexpr uint32_t kSkyBeyond = 0x80000000u;
+F3D_HD uint32_t start_level(uint2 start) { return start.y & ~kSkyBeyond; }
 
 // Ray queues of the wavefront form of a trace batch (f3d_kernels.hip k_wf_primary -> k_wf_occl): k_wf_primary leaves
 // every sample's record with both occlusion verdicts assumed "visible" and files the occlusion rays that have to be

@@ -698,7 +698,18 @@ F3D_HD PrimaryHit sample_primary(const FrameParams &P, uint32_t gx, uint32_t gy,
 #if !defined(F3D_NO_PRIMARY_START)  // A/B builds (tools/build_variant.sh)
     if (P.primary_start) start = P.primary_start[(size_t)(gy - P.row_begin) * P.cam.width + gx];
 #endif
-    ph.hit = closest_hit(P, P.cam.origin, 1e-3f, ph.rd, 1e30f, pend, f_from_bits(start.x), start.y);
+    if (!(Pending::kMesh && P.mesh.traversal_mode == 0u) && certified_sky(start) && sky_shortcut_enabled()) {
+        // No ray of the pixel meets terrain and there is no mesh to walk: closest_hit's miss, without the ray, its root
+        // interval and the scaffolding of a march that ends before its first step (t_clear = 3e38: march_begin_at returns
+        // marching = false whatever the interval is) or walks out of the footprint (kSkyBeyond).  The certificate promises
+        // nothing about triangles.
+        ph.hit.kind = 0u;
+        ph.hit.t = 1e30f;
+        ph.hit.p = V3{0.0f, 0.0f, 0.0f};
+        ph.hit.n = V3{0.0f, 0.0f, 0.0f};
+    } else {
+        ph.hit = closest_hit(P, P.cam.origin, 1e-3f, ph.rd, 1e30f, pend, f_from_bits(start.x), start_level(start));
+    }
     ph.sun_tmax = 1e30f;
     ph.cert = 0xFFFFFFFFu;
 #if !defined(F3D_NO_SUN_CLEAR)  // A/B builds
@@ -859,6 +870,18 @@ F3D_HD void accumulate_sample(Reservoir &cand, V3 &radiance, V3 a, V3 b, float t
         cand.target_pdf = target_pdf;
     }
     radiance = (radiance + a) + b;
+}
+
+// A pixel-frame all of whose samples miss, under a uniform environment (env_radiance returns one value whatever the
+// direction): every sample contributes a = that value, b = +0 and no candidate, so the samples' sum is this ordered sum --
+// accumulate_sample's additions in its order -- around the empty candidate reservoir.  No direction, ray or random number
+// goes into it (the stream is keyed by pixel and frame and carries nothing to the next frame).
+F3D_HD bool env_is_uniform(const EnvDev &E) { return E.width == 0u || E.height == 0u; }
+F3D_HD V3 all_miss_radiance(const FrameParams &P) {
+    const V3 a = env_radiance(P.env, V3{0.0f, 1.0f, 0.0f}), b = V3{0.0f, 0.0f, 0.0f};
+    V3 radiance = V3{0.0f, 0.0f, 0.0f};
+    for (uint32_t s = 0u; s < P.spp; s++) radiance = (radiance + a) + b;
+    return radiance;
 }
 
 // Everything after the sample loop (:549-574) plus the temporal pass; returns Welford m2.

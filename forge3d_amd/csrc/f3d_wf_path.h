@@ -413,7 +413,7 @@ F3D_HD bool closest(const SceneDev &S, V3 o, V3 d, float tmin, SurfaceHitWf &H, 
         MarchState m = march_begin(S.terrain, r, true);
         if (have && camera_pixel != kNoPixel && S.primary_start != nullptr) {
             const uint2 st = S.primary_start[camera_pixel];
-            if (f_from_bits(st.x) > 0.0f) m = march_begin_at(S.terrain, r, f_from_bits(st.x), st.y);
+            if (f_from_bits(st.x) > 0.0f) m = march_begin_at(S.terrain, r, f_from_bits(st.x), start_level(st));
         }
         const TraceHit th = march_terrain_from<false, true>(S.terrain, r, false, m, *wave.pend);
         if (th.hit && th.t < t_best) {
