@@ -192,6 +192,7 @@ ABI = [
     ("f3d_aether_reference_render", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]),
     ("f3d_smoke_composite", C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), C.c_char_p, C.c_size_t]),
     ("f3d_session_fingerprint", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("f3d_session_mesh_tree", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_char_p, C.c_size_t]),
     # re-arm of a live session (no ABI version bump: detected by the symbol)
     ("f3d_session_rearm", C.c_int, [C.c_void_p, _P(RearmDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_render", C.c_int, [C.c_void_p, _P(Out), C.c_char_p, C.c_size_t]),

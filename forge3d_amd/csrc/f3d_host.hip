@@ -1251,6 +1251,41 @@ int f3d_session_fingerprint(f3d_session *s, uint64_t *out, uint32_t count) {
     }
 }
 
+// Diagnostics: the mesh tree this session's frame launches walk, as the device holds it NOW -- what params.mesh names: the
+// cache entry's buffers, or the session's own copy once a re-mesh has refitted it.  info = {form, node_count,
+// triangle_count, 0}; form 0: no tree, 1: BvhNode records (threaded binary), 2: Bvh4Node records.  Null buffers: the sizes
+// only.  The triangle count is the owner's record of the leaf-order buffer (48 bytes a triangle), not index_count / 3.
+int f3d_session_mesh_tree(f3d_session *s, uint32_t info[4], void *nodes, size_t node_capacity_bytes, void *tris, size_t tri_capacity_bytes,
+                          char *err, size_t errlen) {
+    return c_abi(err, errlen, [&] {
+        DeviceGuard g(checked(s).device);
+        if (!info) fail(F3D_STATUS_VALUE, "null info record");
+        hip_check(hipStreamSynchronize(s->stream), "mesh tree");
+        for (auto &b : s->bands)
+            if (b.stream) hip_check(hipStreamSynchronize(b.stream), "mesh tree");
+        const MeshDev &M = s->params.mesh;
+        const uint32_t form = M.bvh4_nodes ? 2u : (M.bvh_nodes ? 1u : 0u);
+        const void *d_nodes = form == 2u ? (const void *)M.bvh4_nodes : (const void *)M.bvh_nodes;
+        const uint32_t node_count = form == 2u ? M.bvh4_node_count : (form == 1u ? M.bvh_node_count : 0u);
+        const size_t record = form == 2u ? sizeof(Bvh4Node) : sizeof(BvhNode);
+        const size_t owner_tri_bytes = s->own_mesh.live ? s->own_mesh.tri_bytes : (s->mesh ? s->mesh->tri_bytes : 0);
+        const size_t tri_count = form != 0u && M.bvh_tris ? owner_tri_bytes / (3u * sizeof(float4)) : 0u;
+        info[0] = form;
+        info[1] = node_count;
+        info[2] = (uint32_t)tri_count;
+        info[3] = 0u;
+        const size_t node_bytes = (size_t)node_count * record, tri_bytes = tri_count * 3u * sizeof(float4);
+        if (nodes && node_capacity_bytes < node_bytes)
+            fail(F3D_STATUS_VALUE, "the node buffer holds %zu bytes, the tree has %u records of %zu bytes: %zu", node_capacity_bytes, node_count,
+                 record, node_bytes);
+        if (tris && tri_capacity_bytes < tri_bytes)
+            fail(F3D_STATUS_VALUE, "the triangle buffer holds %zu bytes, the tree has %zu triangles of 48 bytes: %zu", tri_capacity_bytes,
+                 tri_count, tri_bytes);
+        if (nodes && node_bytes) hip_check(hipMemcpy(nodes, d_nodes, node_bytes, hipMemcpyDeviceToHost), "mesh tree nodes");
+        if (tris && tri_bytes) hip_check(hipMemcpy(tris, M.bvh_tris, tri_bytes, hipMemcpyDeviceToHost), "mesh tree triangles");
+    });
+}
+
 int f3d_session_render(f3d_session *s, f3d_terrain_ref_out *out, char *err, size_t errlen) {
     return c_abi(err, errlen, [&] {
         DeviceGuard g(checked(s).device);

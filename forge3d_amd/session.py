@@ -406,6 +406,28 @@ class TerrainSession:
             raise RuntimeError("f3d_session_fingerprint failed")
         return dict(zip(self.FINGERPRINT_FIELDS, (int(v) for v in out)))
 
+    # records of f3d_session_mesh_tree (f3d_scene.h BvhNode / Bvh4Node; a triangle corner: xyz and the bits of w)
+    BVH_NODE = np.dtype([("bmin", "<f4", 3), ("skip", "<u4"), ("bmax", "<f4", 3), ("leaf", "<u4")])
+    BVH4_NODE = np.dtype([("lo_x", "<f4", 4), ("hi_x", "<f4", 4), ("lo_y", "<f4", 4), ("hi_y", "<f4", 4), ("lo_z", "<f4", 4),
+                          ("hi_z", "<f4", 4), ("leaf", "<u4", 4), ("first_child", "<u4"), ("inner", "<u4"), ("pad", "<u4", 2)])
+    BVH_CORNER = np.dtype([("xyz", "<f4", 3), ("w", "<u4")])
+
+    def mesh_tree(self):
+        """Diagnostics (synchronises): ``(form, nodes, tris)`` -- the mesh BVH the frame launches walk, read back from the
+        device as it is now (after a remesh() refit: the session's own tree).  ``form`` 0: no tree (empty arrays), 1: ``nodes``
+        are BVH_NODE records in threaded preorder, 2: BVH4_NODE records; ``tris`` has shape (triangles, 3) of BVH_CORNER in
+        leaf order, the original triangle index in ``tris["w"][:, 0]``."""
+        info = (C.c_uint32 * 4)()
+        self._check(self._lib.f3d_session_mesh_tree(self._handle, info, None, 0, None, 0, self._err, len(self._err)))
+        form, node_count, tri_count = int(info[0]), int(info[1]), int(info[2])
+        nodes = np.zeros(node_count, self.BVH4_NODE if form == 2 else self.BVH_NODE)
+        tris = np.zeros((tri_count, 3), self.BVH_CORNER)
+        self._check(self._lib.f3d_session_mesh_tree(self._handle, info, nodes.ctypes.data, nodes.nbytes, tris.ctypes.data, tris.nbytes,
+                                                    self._err, len(self._err)))
+        if (int(info[0]), int(info[1]), int(info[2])) != (form, node_count, tri_count):
+            raise RuntimeError("f3d_session_mesh_tree: the tree changed between the two calls")
+        return form, nodes, tris
+
     def enqueue_frame_part(self, frame: int, part: int, collect_stats: bool = False):
         """One frame in two launches: part 1 = head + the strip's edge rows (the halo donors), part 2 = interior."""
         self._check(self._lib.f3d_session_enqueue_frame_part(self._handle, int(frame), int(part),

@@ -505,6 +505,19 @@ uint32_t f3d_halo_rows(void);
  * [14] accumulation + Welford, [15] frame-head records.  Synchronises the session.  count >= 16. */
 int f3d_session_fingerprint(f3d_session *session, uint64_t *out, uint32_t count);
 
+/* Diagnostics (no ABI version bump: detected by the symbol): the mesh BVH this session's frame launches walk, read back from
+ * the device as it is NOW -- the shared cache entry's tree, or the session's own copy once f3d_session_remesh has refitted
+ * it.  info = {form, node_count, triangle_count, 0}; form 0: the session walks no tree (no mesh), 1: node_count records of
+ * 32 bytes {f32 bmin[3], u32 skip, f32 bmax[3], u32 leaf} in threaded preorder (node i's first child is i + 1, skip = the
+ * node after its subtree, leaf = 0 or (first triangle << 3) | count), 2: node_count records of 128 bytes {f32 lo_x[4],
+ * hi_x[4], lo_y[4], hi_y[4], lo_z[4], hi_z[4], u32 leaf[4], first_child, inner, pad[2]} (slots [0, inner) are the records
+ * first_child + slot, the others leaves or empty: both planes +inf, leaf 0).  Triangles: 3 x {f32 xyz, w} each in leaf
+ * order, the original triangle index as the bits of corner 0's w.  nodes / tris NULL: the sizes only; otherwise exactly
+ * node_count records and 3 * triangle_count corners are written, and a capacity below that is F3D_STATUS_VALUE.
+ * Synchronises the session. */
+int f3d_session_mesh_tree(f3d_session *session, uint32_t info[4], void *nodes, size_t node_capacity_bytes, void *tris,
+                          size_t tri_capacity_bytes, char *err, size_t errlen);
+
 /* Diagnostics (only in builds with -DF3D_WAVE_TIMES; F3D_STATUS_VALUE otherwise): every frame-kernel workgroup
  * writes its {start, end} wall clock (100 MHz ticks) to device_buffer[2 * workgroup]; NULL switches it off. */
 int f3d_session_debug_wave_times(f3d_session *session, void *device_buffer);
