@@ -419,7 +419,10 @@ F3D_HD void march_leaf_interval(const TerrainDev &T, const RayCtx &r, uint32_t c
     hi = f_min(f_min(f_max(tx0, tx1), f_max(tz0, tz1)), r.tmax);
 }
 // hit_cell: the cell (cx | cz << 16) of the hit a closest-hit drain ends with (the sharing of closest-hit rays, march_shared_closest)
-template <bool FUSE = false, class Ctx>
+// VERDICT (any-hit rays): the caller reads res.hit alone, and of res.t only that it is below the ray's tmax and 1e30 -- a clear
+// crossing is then a hit without its root (f3d_trace.h leaf_shortcut).  Its `t < res.t` below is implied: res.t is still the
+// ray's tmax (the first hit ends the drain and the march), and leaf_finish returns t0 < tmax for such a leaf.
+template <bool FUSE = false, bool VERDICT = false, class Ctx>
 F3D_HD void march_drain(const TerrainDev &T, const RayCtx &r, bool any_hit, MarchState &m, uint32_t &queued,
                         TraceHit &res, Ctx &ctx, uint32_t &hit_cell) {
     uint32_t k = 0u;  // per lane: a tie entry is visited twice
@@ -461,10 +464,10 @@ F3D_HD void march_drain(const TerrainDev &T, const RayCtx &r, bool any_hit, Marc
                 const LeafRec leaf = T.leaves[tiled_index(cx, cz, T.tiles_x[0])];
                 float t;
                 if (!(tie && band_rejects(r, lo, hi, min4(leaf), max4(leaf))) &&
-                    leaf_solve(T, r, leaf, cx, cz, lo, hi, any_hit, t) && t < res.t) {
+                    leaf_solve<VERDICT>(T, r, leaf, cx, cz, lo, hi, any_hit, t) && t < res.t) {
                     res.hit = true;  // first hit in ray order is final (see the header)
                     res.t = t;
-                    res.n = leaf_normal(T, leaf, along(r.o, t, r.d), cx, cz);
+                    if (!VERDICT) res.n = leaf_normal(T, leaf, along(r.o, t, r.d), cx, cz);  // (a verdict has no normal: t may be a stand-in)
                     hit_cell = cx | (cz << 16);
                 }
             }
@@ -494,11 +497,11 @@ F3D_HD void march_drain(const TerrainDev &T, const RayCtx &r, bool any_hit, Marc
     // (once, here: a second boolean carried through the loop above costs a lane-mask merge per level of nesting -- 1.4 %)
     m.marching = m.marching & !res.hit;
 }
-template <bool FUSE = false, class Ctx>
+template <bool FUSE = false, bool VERDICT = false, class Ctx>
 F3D_HD void march_drain(const TerrainDev &T, const RayCtx &r, bool any_hit, MarchState &m, uint32_t &queued,
                         TraceHit &res, Ctx &ctx) {
     uint32_t hit_cell;  // (nobody reads it: the stores go)
-    march_drain<FUSE>(T, r, any_hit, m, queued, res, ctx, hit_cell);
+    march_drain<FUSE, VERDICT>(T, r, any_hit, m, queued, res, ctx, hit_cell);
 }
 
 // ---- the last few rays of a wave, shared by all its lanes -----------------------------------------
@@ -667,7 +670,7 @@ F3D_HD bool march_shared(const TerrainDev &T, const RayCtx &own_ray, MarchState 
 #endif
             again = round + 1u < kShareRounds && ctx.share_now(m.marching);
             if (again || ctx.flush_now(queued, m.marching)) {
-                march_drain<FUSE>(T, s.r, true, m, queued, res, ctx);
+                march_drain<FUSE, true>(T, s.r, true, m, queued, res, ctx);  // (a slice posts its verdict, nothing else)
                 if (res.hit) ctx.verdict_set(s.owner);
                 if (ctx.verdict_get(s.owner)) m.marching = false;  // another slice of this ray has hit
             }
@@ -786,7 +789,8 @@ F3D_HD MarchState march_begin_at(const TerrainDev &T, const RayCtx &r, float t_c
 // Ctx provides: note(), band_entry(), the FIFO storage fifo_put/fifo_get, the wave votes
 // flush_now(queued, marching) / any(pred), and share_now / deal / verdict_* (ray sharing).
 // hit_cell (closest-hit callers that want it, no ray sharing): the cell (cx | cz << 16) of the hit.
-template <bool CURVED, bool STOP = CURVED, bool FUSE = false, class Ctx>
+// VERDICT: an any-hit caller that reads only `hit` and `t < min(tmax, 1e30)` of the answer (march_drain).
+template <bool CURVED, bool STOP = CURVED, bool FUSE = false, bool VERDICT = false, class Ctx>
 F3D_HD TraceHit march_terrain_from(const TerrainDev &T, const RayCtx &r, bool any_hit, MarchState m, Ctx &ctx,
                                    float t_stop = 3.0e38f, uint32_t *hit_cell = nullptr) {
     TraceHit res;
@@ -824,7 +828,7 @@ F3D_HD TraceHit march_terrain_from(const TerrainDev &T, const RayCtx &r, bool an
 #endif
         // (Balancing the queued leaf solves of a wave over its lanes -- ceil(sum / lanes) rounds instead of
         // max(queued), the owner's ray fetched by ds_bpermute -- was built and measured: bit-identical, 0.96x.)
-        if (deal || ctx.flush_now(queued, m.marching)) march_drain<FUSE>(T, r, any_hit, m, queued, res, ctx, cell);
+        if (deal || ctx.flush_now(queued, m.marching)) march_drain<FUSE, VERDICT>(T, r, any_hit, m, queued, res, ctx, cell);
         if (deal || !ctx.any(m.marching || queued != 0u)) break;
     }
     if (hit_cell) *hit_cell = cell;
@@ -838,10 +842,10 @@ F3D_HD TraceHit march_terrain_from(const TerrainDev &T, const RayCtx &r, bool an
     return res;
 }
 
-template <bool CURVED, bool FUSE = false, class Ctx>
+template <bool CURVED, bool FUSE = false, bool VERDICT = false, class Ctx>
 F3D_HD TraceHit march_terrain(const TerrainDev &T, const RayCtx &r, bool any_hit, bool start_in_cell, Ctx &ctx,
                               float t_stop = 3.0e38f) {
-    return march_terrain_from<CURVED, true, FUSE>(T, r, any_hit, march_begin(T, r, start_in_cell), ctx, t_stop);
+    return march_terrain_from<CURVED, true, FUSE, VERDICT>(T, r, any_hit, march_begin(T, r, start_in_cell), ctx, t_stop);
 }
 
 // ---- a STREAM of occlusion rays through the lanes of a wave (wavefront kernels, f3d_kernels.hip k_wf_occl) -----------

@@ -437,8 +437,9 @@ F3D_HD bool occluded(const FrameParams &P, V3 o, float tmin, V3 d, float tmax, b
     // rays carry the curvature policy (apply_curvature is a compile-time constant per call site).
     // (with the curvature policy switched off for the whole render, c2 = 0 and fma(t*t, 0, y) == y: the
     // curved instantiation then computes the flat answers exactly, so there is no third copy of the march)
-    TraceHit th = apply_curvature ? march_terrain<true, kFuse>(P.terrain, r, true, true, pend, terrain_tmax)
-                                  : march_terrain<false, kFuse>(P.terrain, r, true, true, pend, terrain_tmax);
+    // (VERDICT: only `hit` and `t < min(tmax, 1e30)` are read below -- clear crossings are hits without their root)
+    TraceHit th = apply_curvature ? march_terrain<true, kFuse, true>(P.terrain, r, true, true, pend, terrain_tmax)
+                                  : march_terrain<false, kFuse, true>(P.terrain, r, true, true, pend, terrain_tmax);
 #endif
     bool hit = th.hit && th.t < tmax && th.t < 1e30f;
 #if !defined(F3D_MESH_FIRST) && !defined(F3D_TIMING_NO_MESH_ANY)

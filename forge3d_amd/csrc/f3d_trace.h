@@ -29,6 +29,9 @@
 
 #include "f3d_build.h"
 #include "f3d_scene.h"
+#if !defined(__HIPCC__)
+#include <cstdlib>  // getenv: leaf_shortcut_enabled
+#endif
 
 namespace f3d {
 
@@ -114,7 +117,151 @@ F3D_HD bool ray_triangle(V3 o, float tmin, V3 d, float tmax, V3 v0, V3 v1, V3 v2
     return false;
 }
 
+// ---- leaf solves whose outcome can be read off the coefficients ---------------------------------------
+// leaf_solve evaluates the ray against the patch at three parameters and forms the quadratic a s^2 + b s + c of the
+// clearance over s in [0, 1]; what follows -- the reference's root finder (:205-235: a square root, up to three divisions,
+// the root selection and the interval tests) -- is a deterministic function of the FLOATS a, b, c, dv[2], t0, t1 and of
+// (any_hit, tmin, tmax) alone.  leaf_shortcut predicts that function for three kinds of leaf; the arguments below are
+// about those floats and the rounded operations of leaf_finish, never about the geometry, so curvature, clamped (u, v)
+// and zero-length intervals (t0 == t1: a = b = 0) need no case of their own.  Every comparison is written so that a NaN
+// fails it: what is not claimed takes the full path.  (tests/leaf_host runs the full path beside every claim: 2 * 10^8
+// synthetic leaves on and around every threshold, and every leaf the marches of the test scenes queue.)
+//
+// With p(s) = a s^2 + b s + c over the reals, S = |a| + |b| + |c| and tau = 2^-10.  c > 0 in all three (the
+// `any_hit && c <= 0` answer comes first, as in the reference).
+//
+//  MISS B, "increasing from a positive start":  1e-30 < c < 1e30,  4 |a| < b < 1e6.
+//    Linear branch (|a| < 1e-12): s = -c / b with c / b >= 1e-36, no underflow, so s < 0 (or b <= 1e-12: no root asked for).
+//    Quadratic branch: b^2 < 1e12 and |4 a c| < b c < 1e36 are finite, so disc < 0 (a miss) or sq is finite and
+//    q = -(b + sq) / 2 <= -b / 2 < 0.  r0 = q / a with |q| >= b / 2 > 2 |a|: below -2 for a > 0, above 2 for a < 0.
+//    r1 = c / q (or 1e30 for a tiny q) is negative and no -0, the one way `>= 0` could accept it: sq <= b + sqrt(b c)
+//    gives |q| <= b + sqrt(b c) / 2, hence c / |q| >= min(2 / 3, c / (1.5 b)) >= 6e-37.  Neither root is in [0, 1].
+//    This is the origin cell of a secondary ray: c ~ 1e-3 there and a is rounding noise of heights of thousands of
+//    metres, which no relative margin survives.
+//    (The caps: beyond them b * b or 4 a c overflow, sq = inf, and c / -inf = -0 IS accepted by the reference's `>= 0`.)
+//
+//  MISS A, "positive at both ends, cannot dip to zero between":  min(c, dv[2]) - max(a, 0) / 4 > tau S,  c < 1e15,
+//    and in the linear branch (|a| < 1e-12, where the reference ignores a) also b + c > tau c.
+//    b = (dv[2] - dv[0]) - a rounds twice, so p(1) = a + b + c is dv[2] to within 2^-21 S.  On [0, 1], p is its chord
+//    minus a s (1 - s) <= max(a, 0) / 4, so p >= (tau - 2^-21) S > 0 there.  The roots the stable formula returns are
+//    roots of a quadratic whose coefficients differ from a, b, c by a few ulp (disc by fma; S < 1e18 keeps b^2 and 4 a c
+//    finite, |a| >= 1e-12 with c > tau |a| keeps 4 a c normal), i.e. of a p~ with |p~ - p| < 2^-19 S on [0, 1]: none lies in
+//    [0, 1], with a margin of 2^9 error bounds; and none rounds to +-0 (r0 r1 = c / a >= tau with |q| <= 1.5 S:
+//    |r1| >= tau / 1.5, |r0| >= sqrt(tau) by |q| >= sqrt(|a| c) whenever disc >= 0).
+//    Linear branch: c > tau S >= tau |b| keeps c / |b| from underflowing; b > 0 gives s < 0, b < 0 with b + c > tau c
+//    gives s = c / |b| >= 1 / (1 - tau) > 1.
+//
+//  CLEAR CROSSING, for a caller that consumes the VERDICT alone:  c > tau S,  dv[2] < -tau S,  c < 1e15,  |a| >= 1e-12,
+//    and both t0 and t_far = (t1 - t0) + t0 inside (tmin, min(tmax, 1e30)).
+//    p~(0) > 0 > p~(1) for the quadratic the formula solves exactly (as above), so it has one root in (0, 1) and the other
+//    outside [0, 1], each at least tau / 4 from 0 and from 1 (|p~'| <= 4 S on [-1, 2]) -- ulps of rounding in the
+//    divisions move neither across.  The reference takes that root as s_hit in (0, 1), and t = fma(s_hit, t1 - t0, t0) lies
+//    between fma(0, ...) = t0 and fma(1, ...) = t_far (rounding is monotone, whatever the sign of t1 - t0): inside
+//    (tmin, tmax) and below 1e30 when both ends are -- a hit.  t_hit is set to t0, which shares those properties;
+//    NOT for callers that read t or the normal (closest-hit rays, the G-buffer, k_query's pick, the tracers' closest hits).
+//
+//  The margins are taken off term by term, x - tau |a| - tau |b| - tau |c| rounded after each (leaf_less_margin), which is
+//  tau S to within ulps of S and keeps ONE value live where the sum S beside x costs the frame kernel a scratch slot;
+//  c < 1e15 with c > tau S bounds S < 2^10 c < 1.1e18.
+constexpr float kLeafTau = 0.0009765625f;  // 2^-10
+enum : int { kLeafFull = 0, kLeafMissA = 1, kLeafMissB = 2, kLeafCross = 3 };
+
+// x - tau (|a| + |b| + |c|), rounded after each term
+F3D_HD float leaf_less_margin(float x, float abs_a, float b, float c) {
+    x = f_fma(-kLeafTau, abs_a, x);
+    x = f_fma(-kLeafTau, f_abs(b), x);
+    return f_fma(-kLeafTau, f_abs(c), x);
+}
+
+F3D_HD int leaf_shortcut(float a, float b, float c, float dv2, float t0, float t1, float tmin, float tmax) {
+    const float abs_a = f_abs(a);
+    if (c > 1e-30f && c < 1e30f && b < 1e6f && b > 4.0f * abs_a) return kLeafMissB;
+    const bool quadratic = abs_a >= 1e-12f;
+    if (c < 1e15f) {  // (with c > tau S below: S < 2^10 c < 1e18)
+        const float clear = leaf_less_margin(f_min(c, dv2) - 0.25f * f_max(a, 0.0f), abs_a, b, c);
+        if (clear > 0.0f && (quadratic || b + c > kLeafTau * c)) return kLeafMissA;
+        if (quadratic && leaf_less_margin(f_min(c, -dv2), abs_a, b, c) > 0.0f) {
+            const float t_far = (t1 - t0) + t0;  // = fma(1, t1 - t0, t0): the hit parameter at s_hit = 1
+            const float cap = f_min(tmax, 1e30f);  // (compared one by one: fmin / fmax would drop a NaN)
+            if (t0 > tmin && t_far > tmin && t0 < cap && t_far < cap) return kLeafCross;
+        }
+    }
+    return kLeafFull;
+}
+
+// The tests' switch and tap, in host-only builds of these headers (tests/emul, tests/leaf_host) alone: with
+// F3D_EMUL_NO_LEAF_SHORTCUT set (or leaf_shortcut_force() == 0) every leaf takes the full path; a tap sees every leaf
+// the marchers solve (tests/leaf_host counts what each test settles and runs both paths on it).  The device library
+// has neither.
+#if defined(__HIPCC__)
+F3D_HD bool leaf_shortcut_enabled() { return true; }
+#else
+inline int &leaf_shortcut_force() {  // -1: ask the environment; 0 / 1: off / on (per thread)
+    static thread_local int force = -1;
+    return force;
+}
+inline bool leaf_shortcut_enabled() {
+    const int force = leaf_shortcut_force();
+    return force >= 0 ? force != 0 : getenv("F3D_EMUL_NO_LEAF_SHORTCUT") == nullptr;
+}
+using LeafTap = void (*)(const RayCtx &r, const float *dv, float t0, float t1, bool any_hit, bool verdict_only);
+inline LeafTap &leaf_tap() {
+    static LeafTap tap = nullptr;
+    return tap;
+}
+#endif
+
+// The second half of terrain_leaf_intersect (:196-235) from the three clearances dv[0..2] at t0, (t0 + t1) / 2, t1.
+// VERDICT: the caller reads nothing of the hit but that there is one (and `t_hit < its best t`, see march_drain).
+template <bool VERDICT = false>
+F3D_HD bool leaf_finish(const RayCtx &r, const float *dv, float t0, float t1, bool any_hit, float &t_hit) {
+#if !defined(__HIPCC__)
+    if (leaf_tap()) leaf_tap()(r, dv, t0, t1, any_hit, VERDICT);
+#endif
+    float c = dv[0];
+    float a = 2.0f * dv[2] + 2.0f * dv[0] - 4.0f * dv[1];
+    float b = dv[2] - dv[0] - a;
+    float s_hit = 1e30f;
+    if (any_hit && c <= 0.0f) {
+        s_hit = 0.0f;
+    } else {
+        const int known = leaf_shortcut_enabled() ? leaf_shortcut(a, b, c, dv[2], t0, t1, r.tmin, r.tmax) : kLeafFull;
+        if (known == kLeafMissA || known == kLeafMissB) return false;
+        if (VERDICT && any_hit && known == kLeafCross) {  // (any-hit rays only: a closest-hit ray wants the root itself)
+            t_hit = t0;
+            return true;
+        }
+        if (f_abs(a) < 1e-12f) {
+            if (f_abs(b) > 1e-12f) {
+                float s = -c / b;
+                if (s >= 0.0f && s <= 1.0f) s_hit = s;
+            }
+        } else {
+            float four_ac = 4.0f * a * c;
+            float disc = f_fma(b, b, -four_ac);
+            if (disc >= 0.0f) {
+                float sq = f_sqrt(disc);
+                float q = -0.5f * (b + (b >= 0.0f ? sq : -sq));
+                float r0 = q / a;
+                float r1 = (f_abs(q) < 1e-30f) ? 1e30f : c / q;
+                float lo = f_min(r0, r1), hi = f_max(r0, r1);
+                if (lo >= 0.0f && lo <= 1.0f) s_hit = lo;
+                else if (hi >= 0.0f && hi <= 1.0f) s_hit = hi;
+            }
+        }
+    }
+    if (s_hit <= 1.0f) {
+        float t = f_fma(s_hit, t1 - t0, t0);
+        if (t > r.tmin && t < r.tmax) {
+            t_hit = t;
+            return true;
+        }
+    }
+    return false;
+}
+
 // Exact ray / bilinear patch solve (terrain_leaf_intersect, :167-235) on a corner record.
+template <bool VERDICT = false>
 F3D_HD bool leaf_solve(const TerrainDev &T, const RayCtx &r, const LeafRec &h, uint32_t cx, uint32_t cz, float t0,
                        float t1, bool any_hit, float &t_hit) {
     float tm = 0.5f * (t0 + t1);
@@ -130,38 +277,7 @@ F3D_HD bool leaf_solve(const TerrainDev &T, const RayCtx &r, const LeafRec &h, u
         float hh = mix(mix(h.h00, h.h10, u), mix(h.h01, h.h11, u), v);
         dv[i] = height_at(r, t) - hh;
     }
-    float c = dv[0];
-    float a = 2.0f * dv[2] + 2.0f * dv[0] - 4.0f * dv[1];
-    float b = dv[2] - dv[0] - a;
-    float s_hit = 1e30f;
-    if (any_hit && c <= 0.0f) {
-        s_hit = 0.0f;
-    } else if (f_abs(a) < 1e-12f) {
-        if (f_abs(b) > 1e-12f) {
-            float s = -c / b;
-            if (s >= 0.0f && s <= 1.0f) s_hit = s;
-        }
-    } else {
-        float four_ac = 4.0f * a * c;
-        float disc = f_fma(b, b, -four_ac);
-        if (disc >= 0.0f) {
-            float sq = f_sqrt(disc);
-            float q = -0.5f * (b + (b >= 0.0f ? sq : -sq));
-            float r0 = q / a;
-            float r1 = (f_abs(q) < 1e-30f) ? 1e30f : c / q;
-            float lo = f_min(r0, r1), hi = f_max(r0, r1);
-            if (lo >= 0.0f && lo <= 1.0f) s_hit = lo;
-            else if (hi >= 0.0f && hi <= 1.0f) s_hit = hi;
-        }
-    }
-    if (s_hit <= 1.0f) {
-        float t = f_fma(s_hit, t1 - t0, t0);
-        if (t > r.tmin && t < r.tmax) {
-            t_hit = t;
-            return true;
-        }
-    }
-    return false;
+    return leaf_finish<VERDICT>(r, dv, t0, t1, any_hit, t_hit);
 }
 
 // terrain_normal_at (:239-248) from the corner record already in registers.
