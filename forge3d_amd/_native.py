@@ -161,6 +161,20 @@ QUERY_TERRAIN_ONLY, QUERY_CURVED, QUERY_DEVICE_POINTERS, QUERY_NO_WAIT = 1, 2, 4
 QUERY_SCRATCH_BYTES_PER_RAY = 80  # F3D_QUERY_SCRATCH_BYTES_PER_RAY
 
 
+class RasterDesc(C.Structure):
+    """f3d_session_raster_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("mode", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("lift", C.c_float), ("target_count", C.c_uint32), ("reserved", C.c_uint32),
+        ("targets", C.c_void_p), ("masks", C.c_void_p), ("count", C.c_void_p),
+    ]
+
+
+RASTER_TOWARD_POINT, RASTER_ALONG_DIRECTION = 0, 1
+RASTER_TERRAIN_ONLY, RASTER_CURVED, RASTER_DEVICE_POINTERS, RASTER_NO_WAIT, RASTER_SESSION_SUN = 1, 2, 4, 8, 16
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -200,6 +214,7 @@ ABI = [
     ("f3d_session_remesh", C.c_int, [C.c_void_p, _P(RemeshDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_reterrain", C.c_int, [C.c_void_p, _P(ReterrainDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_query", C.c_int, [C.c_void_p, _P(QueryDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_raster", C.c_int, [C.c_void_p, _P(RasterDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
     ("f3d_session_halo", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p), _P(C.c_uint64)]),

@@ -13,6 +13,7 @@
 #include "f3d_launch.h"
 #include "f3d_shade.h"
 #include "f3d_query.h"
+#include "f3d_raster.h"
 #include "f3d_lds.h"
 
 namespace f3d {
@@ -814,6 +815,30 @@ __global__ __launch_bounds__(kWave) void k_query(const QueryParams Q) {
     typename PendingFor<MESH>::type pend{make_pending(lds, Q.frame.terrain)};
     const uint32_t i = blockIdx.x * kWave + threadIdx.x;
     if (i < Q.count) query_lane(Q, i, pend);
+}
+
+// DEM visibility rasters on a live session (f3d_session_raster; f3d_raster.h): k_query's shape -- one wave a workgroup, its
+// LdsPending rows -- with a wave owning the 64 consecutive samples [64 b, 64 b + 64) of the region: the wave's ballot after a
+// target IS mask word b of that target, written by one lane with an ordinary store, and nothing is shared between waves.  A
+// lane keeps its sample's origin and its count in registers across the targets.
+template <bool MESH>
+__global__ __launch_bounds__(kWave) void k_raster(const RasterParams R) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+    typename PendingFor<MESH>::type pend{make_pending(lds, R.frame.terrain)};
+    const uint32_t total = R.rows * R.cols, n = blockIdx.x * kWave + threadIdx.x;
+    const size_t words = ((size_t)total + 63u) >> 6;
+    const bool have = n < total;
+    const V3 o = have ? raster_origin(R, n) : V3{0.0f, 0.0f, 0.0f};
+    uint32_t seen = 0u;
+    for (uint32_t k = 0u; k < R.target_count; k++) {  // (wave-uniform: every lane meets the ballot below after every target)
+        const float4 target = R.targets ? R.targets[k] : float4{R.frame.light.wi.x, R.frame.light.wi.y, R.frame.light.wi.z, 0.0f};
+        bool visible = false;
+        if (have) visible = raster_visible(R, o, target, pend);
+        const unsigned long long word = __ballot(visible);
+        if (R.masks && threadIdx.x == 0u) R.masks[(size_t)k * words + blockIdx.x] = word;
+        seen += visible ? 1u : 0u;
+    }
+    if (R.count && have) R.count[n] = seen;
 }
 
 // ---- acceleration-table builders (reference build_minmax_mips,

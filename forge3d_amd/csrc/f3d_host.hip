@@ -130,6 +130,9 @@ struct f3d_session {
     void *query_scratch = nullptr;
     uint64_t query_bytes = 0;
     size_t query_capacity = 0;  // rays
+    // DEM visibility rasters (f3d_session_raster, host form): targets and outputs pass through, grown only for a larger call
+    void *raster_scratch = nullptr;
+    uint64_t raster_bytes = 0;
     TerrainTables tables;
     uint32_t width = 0, height = 0, row_begin = 0, row_end = 0, rows = 0;
     PackedReservoir *res[2] = {nullptr, nullptr};
@@ -957,6 +960,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 #include "f3d_host_halo.h"  // peer halos: the pull kernel, the batch enqueue and their C ABI
 #include "f3d_host_update.h"  // session updates (re-arm, re-aim, re-mesh, re-terrain): one path, their own steps and their C ABI
 #include "f3d_host_query.h"  // ray queries on a live session: checks, scratch, staged copies, launch and their C ABI
+#include "f3d_host_raster.h"  // DEM visibility rasters on a live session: checks, scratch, staged copies, launch and their C ABI
 
 // ---------------------------------------------------------------------------------------
 // C ABI

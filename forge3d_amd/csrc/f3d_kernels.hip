@@ -211,6 +211,14 @@ hipError_t launch_query(const QueryParams &p, hipStream_t stream) {
     else hipLaunchKernelGGL((k_query<false>), grid, block, 0, stream, p);
     return hipGetLastError();
 }
+hipError_t launch_raster(const RasterParams &p, hipStream_t stream) {
+    const uint32_t total = p.rows * p.cols;
+    if (total == 0u || p.target_count == 0u) return hipSuccess;
+    const dim3 grid((total + kWave - 1u) / kWave), block(kWave);
+    if (p.frame.mesh.traversal_mode == 0u) hipLaunchKernelGGL((k_raster<true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((k_raster<false>), grid, block, 0, stream, p);
+    return hipGetLastError();
+}
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream) {
     dim3 block(16, 16), grid((p.leaf_dim_x + 15) / 16, (p.leaf_dim_y + 15) / 16);
     hipLaunchKernelGGL(k_leaf_build, grid, block, 0, stream, p);

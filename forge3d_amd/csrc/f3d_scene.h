@@ -267,4 +267,19 @@ struct QueryParams {
     float *direction;        // mode 2: 3 per ray, the centre ray's direction
 };
 
+// DEM visibility rasters on a live session (f3d_session_raster; k_raster, f3d_raster.h): frame as for a query, one lane a
+// DEM sample of the region, a loop over the targets.  Either output may be null.
+constexpr uint32_t kRasterTowardPoint = 0u, kRasterAlongDirection = 1u;
+struct RasterParams {
+    FrameParams frame;
+    uint32_t mode;               // kRaster*
+    uint32_t curved;             // the sun rays' curvature policy (and, toward a point, the sight line's drop)
+    uint32_t row0, col0, rows, cols;  // the region: sample n = r * cols + c is DEM sample (row0 + r, col0 + c)
+    float lift;                  // added to the sample's height
+    uint32_t target_count;       // >= 1
+    const float4 *targets;       // (x, y, z, w) each; null: one target, frame.light.wi (SESSION_SUN)
+    unsigned long long *masks;   // target_count x ceil(rows * cols / 64) words, bit n & 63 of word n >> 6
+    uint32_t *count;             // rows * cols: targets whose bit is 1
+};
+
 }  // namespace f3d

@@ -360,6 +360,133 @@ class TerrainSession:
         t = self._query(_native.QUERY_CLOSEST, flags, rays, 8, np.float32, ("t",))["t"]
         return (rays[:, 1] - t) if not isinstance(t, np.ndarray) else (np.float32(top) - t)
 
+    # -- DEM visibility rasters: viewshed, sun mask, sun hours -------------------------------
+    SURFACE_BIAS = 1e-3  # rasters start their rays this far above the lifted sample (the shadow rays' own offset)
+
+    def visibility(self, targets, *, toward: bool, curved: bool = False, terrain_only: bool = False, lift: float = 0.0,
+                   region=None, masks: bool = True, count: bool = False, wait: bool = True):
+        """One f3d_session_raster: from every DEM sample of ``region`` (``(row0, col0, rows, cols)``, default the whole DEM),
+        lifted by ``lift``, is each target visible?  ``targets`` (K, 4) float32 rows ``(x, y, z, w)`` ((K, 3): w = 0): with
+        ``toward`` a world position and, for ``w > 0``, a maximum horizontal distance; otherwise a direction as given.
+        ``None`` (directions only) is the session's current sun.  The device builds the rays from the terrain the session
+        holds NOW and marches them as occluded() does (``curved``: with the earth-curvature policy; toward a point the sight
+        line drops with it).  A NumPy array takes the host form (blocking), a torch tensor on the session's device the
+        device form (results are tensors; ``wait=False`` returns with the kernel in flight on the session's stream, and the
+        bits are unpacked on torch's current stream: use it on a session created on that stream).
+        Returns the bool array (K, rows, cols) -- True: visible / lit -- for ``masks``, the uint32 array (rows, cols) of the
+        number of targets seen for ``count`` (int32 bits as a tensor), ``(masks, count)`` for both."""
+        if not (masks or count):
+            raise ValueError("visibility() needs an output: masks, count or both")
+        dem_h, dem_w = self.dem_shape
+        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
+        if min(row0, col0, rows, cols) < 0:
+            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        q = _native.RasterDesc()
+        q.struct_size = C.sizeof(_native.RasterDesc)
+        q.mode = _native.RASTER_TOWARD_POINT if toward else _native.RASTER_ALONG_DIRECTION
+        q.flags = (_native.RASTER_CURVED if curved else 0) | (_native.RASTER_TERRAIN_ONLY if terrain_only else 0)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.lift = float(lift)
+        n = rows * cols
+        words = (n + 63) // 64
+        tensors = type(targets).__module__.split(".")[0] == "torch"
+        if tensors:
+            import torch  # (only for callers who hand tensors in)
+
+            if not targets.is_cuda:
+                raise ValueError("a tensor raster needs a tensor on the session's device (NumPy arrays take the host form)")
+            t = targets.to(torch.float32)
+            if t.ndim != 2 or t.shape[1] not in (3, 4):
+                raise ValueError(f"expected shape (K, 4) or (K, 3), got {tuple(targets.shape)}")
+            if t.shape[1] == 3:
+                t = torch.cat([t, torch.zeros_like(t[:, :1])], 1)
+            t = t.contiguous()
+            k = int(t.shape[0])
+            q.flags |= _native.RASTER_DEVICE_POINTERS | (0 if wait else _native.RASTER_NO_WAIT)
+            q.target_count, q.targets = k, (t.data_ptr() if k else None)
+            # (the kernel writes every word of both; without targets nothing runs and nothing is seen)
+            m_out = torch.empty((k, words), dtype=torch.int64, device=t.device) if masks else None
+            c_out = (torch.empty if k else torch.zeros)(n, dtype=torch.int32, device=t.device) if count else None
+            q.masks, q.count = (m_out.data_ptr() if masks else None), (c_out.data_ptr() if count else None)
+        else:
+            if not wait:
+                raise ValueError("wait=False is for tensor rasters: results in host memory are there when the call returns")
+            if targets is None:
+                if toward:
+                    raise ValueError("targets=None is the session's sun direction: it needs toward=False")
+                q.flags |= _native.RASTER_SESSION_SUN
+                k = 1
+            else:
+                t = np.asarray(targets, dtype=np.float32)
+                if t.ndim != 2 or t.shape[1] not in (3, 4):
+                    raise ValueError(f"expected shape (K, 4) or (K, 3), got {t.shape}")
+                if t.shape[1] == 3:
+                    t = np.concatenate([t, np.zeros((t.shape[0], 1), np.float32)], 1)
+                t = np.ascontiguousarray(t)
+                k = int(t.shape[0])
+                q.target_count, q.targets = k, (t.ctypes.data if k else None)
+            m_out = np.zeros((k, words), np.uint64) if masks else None
+            c_out = np.zeros(n, np.uint32) if count else None
+            q.masks, q.count = (m_out.ctypes.data if masks else None), (c_out.ctypes.data if count else None)
+        self._check(self._lib.f3d_session_raster(self._handle, C.byref(q), self._err, len(self._err)))  # (t lives until here)
+        out = []
+        if masks and tensors:
+            bit = torch.arange(64, dtype=torch.int64, device=m_out.device)
+            out.append((((m_out.unsqueeze(-1) >> bit) & 1) != 0).reshape(k, words * 64)[:, :n].reshape(k, rows, cols))
+        elif masks:
+            bits = np.unpackbits(m_out.view(np.uint8).reshape(k, words * 8), axis=1, bitorder="little")
+            out.append(bits[:, :n].astype(bool).reshape(k, rows, cols))
+        if count:
+            out.append(c_out.reshape(rows, cols))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def viewshed(self, observer, *, observer_height: float = 1.7, target_height: float = 0.0, max_distance=None,
+                 curved: bool = False, terrain_only: bool = False, region=None):
+        """Which DEM samples (raised by ``target_height``) does an observer see?  ``observer``: ``(x, y, z)``, an absolute
+        position, or ``(x, z)``, standing ``observer_height`` above ground(); an (M, 3) / (M, 2) array of observers gives
+        the cumulative viewshed.  ``max_distance``: samples farther away horizontally are not visible.  ``curved``: the
+        sight lines follow the session's earth curvature and refraction (one effective radius for the whole DEM).
+        Returns the bool array (rows, cols), True: visible, for one observer; for several the uint32 array of how many
+        observers see each sample.  An observer outside the DEM's footprint given as ``(x, z)`` sees nothing."""
+        obs = np.asarray(observer, dtype=np.float32)
+        single = obs.ndim == 1
+        obs = np.atleast_2d(obs)
+        if obs.ndim != 2 or obs.shape[1] not in (2, 3):
+            raise ValueError(f"observer must be (x, y, z), (x, z) or an array of them, got shape {np.asarray(observer).shape}")
+        if obs.shape[1] == 2:
+            y = self.ground(obs) + np.float32(observer_height)  # (the terrain: an observer does not stand on the mesh)
+            obs = np.stack([obs[:, 0], y.astype(np.float32), obs[:, 1]], 1)
+            obs = obs[np.isfinite(obs).all(1)]  # (no ground under it: nothing to stand on, nothing seen)
+        w = np.float32(0.0 if max_distance is None else max_distance)
+        if max_distance is not None and not w > 0.0:
+            raise ValueError(f"max_distance must be positive, got {max_distance}")
+        targets = np.concatenate([obs, np.full((len(obs), 1), w, np.float32)], 1).astype(np.float32)
+        lift = np.float32(np.float32(target_height) + np.float32(self.SURFACE_BIAS))
+        if single:
+            if len(targets) == 0:  # (no target is a checked no-op of the library: the region is validated, nothing is seen)
+                return self.visibility(targets, toward=True, curved=curved, terrain_only=terrain_only, lift=lift, region=region,
+                                       masks=False, count=True) != 0
+            return self.visibility(targets, toward=True, curved=curved, terrain_only=terrain_only, lift=lift, region=region)[0]
+        return self.visibility(targets, toward=True, curved=curved, terrain_only=terrain_only, lift=lift, region=region,
+                               masks=False, count=True)
+
+    def shadow_mask(self, direction=None, *, curved: bool = True, terrain_only: bool = False, region=None):
+        """Which DEM samples are lit from ``direction`` (toward the light; None: the session's current sun, as the frames'
+        sun rays use it)?  Returns the bool array (rows, cols), True: lit, as the reference's shadow_mask."""
+        targets = None if direction is None else np.asarray(direction, dtype=np.float32).reshape(1, 3)
+        return self.visibility(targets, toward=False, curved=curved, terrain_only=terrain_only, lift=np.float32(self.SURFACE_BIAS),
+                               region=region)[0]
+
+    def sun_hours(self, directions, *, curved: bool = True, terrain_only: bool = False, region=None):
+        """From how many of ``directions`` (N, 3) is each DEM sample lit?  Returns the uint32 array (rows, cols).  A direction
+        with ``y <= 0`` (the sun below the horizontal) is dropped here and lights nothing."""
+        d = np.asarray(directions, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError(f"expected shape (N, 3), got {d.shape}")
+        d = d[d[:, 1] > 0.0]
+        return self.visibility(d, toward=False, curved=curved, terrain_only=terrain_only, lift=np.float32(self.SURFACE_BIAS),
+                               region=region, masks=False, count=True)
+
     def certificates(self) -> dict:
         """Diagnostics (synchronises): content hashes of the sun-ray and primary-ray certificates."""
         out = (C.c_uint64 * 2)()

@@ -473,6 +473,55 @@ typedef struct f3d_session_query_desc {
     float *direction;     /* count x 3, mode 2 only: the centre ray's direction */
 } f3d_session_query_desc;
 int f3d_session_query(f3d_session *session, const f3d_session_query_desc *desc, char *err, size_t errlen);
+/* ---- DEM visibility rasters: viewshed, sun mask, sun hours ----------------------------------------------------------------
+ * One question of EVERY DEM sample of a region, the rays built on the device from the terrain the session holds and marched
+ * with the occlusion query's any-hit march (k_raster, csrc/f3d_raster.h): no ray list goes up, one bit per sample per target
+ * comes down.  All arithmetic is f32, one rounding per operation.  Sample n = r * cols + c of the region is DEM sample
+ * (row0 + r, col0 + c); its ray starts at (origin_x + col * spacing_x, height * exaggeration + lift, origin_z + row * spacing_z)
+ * (each plane one fma).  A target is four f32 (x, y, z, w):
+ *   F3D_RASTER_TOWARD_POINT     (x, y, z) is a world position (a viewshed's observer): the ray is origin -> position, t in
+ *                               [0, 1].  CURVED on a scene with earth curvature lowers the direction's y by
+ *                               hd2 * inv_two_r_prime (hd2 the squared horizontal distance), so that the curved march meets the
+ *                               position's own height above its datum at t = 1.  w > 0: a maximum horizontal distance,
+ *                               hd2 > w * w answers 0 without a march
+ *   F3D_RASTER_ALONG_DIRECTION  (x, y, z) is the ray's direction as given (a sun mask), t in [0, 1e30]; w is reserved: 0
+ * SESSION_SUN (ALONG_DIRECTION, target_count 0, targets NULL): one target, the direction the frames' sun rays use NOW.
+ * Bit 1 = visible / lit; 0 = blocked, beyond the distance limit, or a ray the occlusion query would not march (a non-finite
+ * component, a zero direction: an observer exactly on the lifted sample).
+ *   masks  target_count x ceil(rows * cols / 64) uint64: bit n of target k is bit (n & 63) of word k * words + (n >> 6); pad bits 0
+ *   count  rows * cols uint32: the number of targets whose bit is 1
+ * Either may be NULL, not both.  TERRAIN_ONLY, CURVED, DEVICE_POINTERS, NO_WAIT and the ordering on the session stream are
+ * the ray query's; nothing a frame launch reads is written.
+ *   host pointers (default)  blocking; targets go up and the outputs come down through the pinned staging pair via a scratch
+ *       buffer of the session (16 bytes a target + the outputs asked for), grown only for a larger call than any before --
+ *       against memory_budget_bytes (too small: status 2, session unchanged).  Non-finite targets: refused
+ *   DEVICE_POINTERS          targets (16-byte aligned), masks and count are device memory; nothing is copied or allocated
+ * Refused (status 1, session unchanged): an unknown mode or flag, a region that is empty or reaches outside the DEM, a
+ * non-finite lift, SESSION_SUN with targets or toward a point, NO_WAIT without DEVICE_POINTERS, both outputs NULL.
+ * target_count == 0 without SESSION_SUN is a successful no-op.  No ABI version bump: detected by the symbol f3d_session_raster. */
+#define F3D_RASTER_TOWARD_POINT 0u
+#define F3D_RASTER_ALONG_DIRECTION 1u
+#define F3D_RASTER_TERRAIN_ONLY 1u
+#define F3D_RASTER_CURVED 2u
+#define F3D_RASTER_DEVICE_POINTERS 4u
+#define F3D_RASTER_NO_WAIT 8u
+#define F3D_RASTER_SESSION_SUN 16u
+typedef struct f3d_session_raster_desc {
+    uint32_t struct_size;  /* = sizeof(f3d_session_raster_desc) of the caller's header */
+    uint32_t mode;         /* F3D_RASTER_TOWARD_POINT / _ALONG_DIRECTION */
+    uint32_t flags;        /* F3D_RASTER_TERRAIN_ONLY | _CURVED | _DEVICE_POINTERS | _NO_WAIT | _SESSION_SUN */
+    uint32_t row0;         /* the region, in DEM samples: rows [row0, row0 + rows), columns [col0, col0 + cols) */
+    uint32_t col0;
+    uint32_t rows;
+    uint32_t cols;
+    float lift;            /* added to every sample's height (a viewshed's target height, a shadow mask's bias) */
+    uint32_t target_count;
+    uint32_t reserved;     /* 0 */
+    const float *targets;  /* target_count x 4 f32 */
+    uint64_t *masks;       /* target_count x ceil(rows * cols / 64), or NULL */
+    uint32_t *count;       /* rows * cols, or NULL */
+} f3d_session_raster_desc;
+int f3d_session_raster(f3d_session *session, const f3d_session_raster_desc *desc, char *err, size_t errlen);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);
