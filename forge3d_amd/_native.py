@@ -175,6 +175,24 @@ RASTER_TOWARD_POINT, RASTER_ALONG_DIRECTION = 0, 1
 RASTER_TERRAIN_ONLY, RASTER_CURVED, RASTER_DEVICE_POINTERS, RASTER_NO_WAIT, RASTER_SESSION_SUN = 1, 2, 4, 8, 16
 
 
+class DrapeDesc(C.Structure):
+    """f3d_session_drape_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("image", C.c_void_p),
+        ("rows", C.c_uint32), ("cols", C.c_uint32), ("channels", C.c_uint32), ("filter", C.c_uint32),
+        ("scale_x", C.c_float), ("offset_x", C.c_float), ("scale_z", C.c_float), ("offset_z", C.c_float),
+        ("at_row", C.c_uint32), ("at_col", C.c_uint32),
+        ("aim", ReaimDesc),
+    ]
+
+
+DRAPE_NEAREST, DRAPE_BILINEAR = 0, 1
+DRAPE_DEVICE_POINTERS, DRAPE_NO_WAIT, DRAPE_PATCH = 4, 8, 16
+DRAPE_MAX_SIDE = 16384  # F3D_DRAPE_MAX_SIDE
+DRAPE_TEXEL_MAX = 65504.0  # the largest finite binary16
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -215,6 +233,8 @@ ABI = [
     ("f3d_session_reterrain", C.c_int, [C.c_void_p, _P(ReterrainDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_query", C.c_int, [C.c_void_p, _P(QueryDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_raster", C.c_int, [C.c_void_p, _P(RasterDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_drape", C.c_int, [C.c_void_p, _P(DrapeDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
     ("f3d_session_halo", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p), _P(C.c_uint64)]),

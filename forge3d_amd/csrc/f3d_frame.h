@@ -184,7 +184,7 @@ __device__ __forceinline__ void publish_window_stats(const FrameParams &P, bool 
 // pixel-parallel launch (k_head) and leaves an 8-byte record per pixel; the short tail runs on
 // sample lane 0.
 // (`valid` masks the lanes outside the image: every lane of the wave runs the function to its end.)
-template <uint32_t S, class Pending>
+template <uint32_t S, bool DRAPE = false, class Pending>
 __device__ __forceinline__ float frame_lanes(const FrameParams &P, uint32_t tile, bool valid, Pending &pend) {
     constexpr uint32_t kGroup = (1u << S) - 1u;
     // Register budget (round 4).  At 80 VGPRs the marches leave room for ~25 values of the frame; what does not fit lives
@@ -262,7 +262,7 @@ __device__ __forceinline__ float frame_lanes(const FrameParams &P, uint32_t tile
         if (act) {
             uint32_t rng = ph.rng;
             const bool prev_valid = (park[(kParkHead + 1) * kWave] & kHeadPrevValid) != 0u;
-            q = sample_shade_sun(P, prev_valid, [park]() { return f_from_bits(park[kParkHead * kWave]); }, ph, rng, o, pend);
+            q = sample_shade_sun<DRAPE>(P, prev_valid, [park]() { return f_from_bits(park[kParkHead * kWave]); }, ph, rng, o, pend);
         }
         // (Sorting the IBL rays of a 4-wave workgroup by cos(normal, ray) -- a good predictor of the march
         // length, 1.6x fewer IBL wave iterations in the step-log model -- was built and measured: bit-identical,
@@ -716,19 +716,18 @@ __global__ __launch_bounds__(kWave) void k_head(const FrameParams P) {
 // S: sample lanes per pixel (1 = frame_pixel; 2, 4, 8 = frame_lanes).
 // MESH: the scene may hold a mesh (FrameParams::mesh.traversal_mode == 0); terrain-only renders run the instantiation
 // without the mesh walk.
-template <int VARIANT, int MIN_WAVES = 1, uint32_t S = 1u, bool MESH = false>
-__global__ __launch_bounds__(kWave, MIN_WAVES) void k_frame(const FrameParams P) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+template <uint32_t S, bool MESH, bool DRAPE>
+__device__ __forceinline__ void frame_wave(const FrameParams &P, uint32_t *lds) {
     const unsigned long long t_start = wall_clock64();  // 100 MHz: the wave's cost for the next tile ordering
     typename PendingFor<MESH>::type pend{make_pending(lds, P.terrain)};
     uint32_t gx = 0u, gy = 0u, tile;
     const bool active = tile_pixel<S>(P, gx, gy, tile, P.tile_order);
     float m2 = 0.0f;
     if constexpr (S == 1u) {
-        if (active) m2 = frame_pixel(P, gx, gy, pend);
+        if (active) m2 = frame_pixel<DRAPE>(P, gx, gy, pend);
         if (P.collect_stats != 0u) publish_window_stats(P, active, m2);
     } else {
-        m2 = frame_lanes<S>(P, tile, active, pend);
+        m2 = frame_lanes<S, DRAPE>(P, tile, active, pend);
         if (P.collect_stats != 0u) publish_window_stats(P, active && (lane_now() & (S - 1u)) == 0u, m2);
     }
     if (lane_now() == 0u) {  // (one wave per workgroup)
@@ -741,6 +740,19 @@ __global__ __launch_bounds__(kWave, MIN_WAVES) void k_frame(const FrameParams P)
         }
 #endif
     }
+}
+template <int VARIANT, int MIN_WAVES = 1, uint32_t S = 1u, bool MESH = false>
+__global__ __launch_bounds__(kWave, MIN_WAVES) void k_frame(const FrameParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+    frame_wave<S, MESH, false>(P, lds);
+}
+// The frame of a draped session (f3d_session_drape): k_frame with the terrain's albedo sampled from P.drape per primary
+// hit (f3d_shade.h sample_shade_setup<true>).  A kernel of its own, so that the undraped instantiations keep their names,
+// their code and their register budget; MIN_WAVES is this kernel's own budget.
+template <int MIN_WAVES, uint32_t S, bool MESH>
+__global__ __launch_bounds__(kWave, MIN_WAVES) void k_frame_drape(const FrameParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+    frame_wave<S, MESH, true>(P, lds);
 }
 
 __global__ __launch_bounds__(kWave) void k_gbuffer(const FrameParams P, float4 *gbuffer_n, float *depth) {
@@ -782,6 +794,26 @@ __global__ __launch_bounds__(kWave) void k_resolve(const ResolveParams R) {
         if (valid) atomicOr(&R.frame.stats[2], 1u);
         if (bad) atomicOr(&R.frame.stats[3], 1u);
     }
+}
+
+// The resolve of a draped session: k_resolve with the albedo AOV of terrain pixels sampled from the drape (resolve_pixel<true>).
+__global__ __launch_bounds__(kWave) void k_resolve_drape(const ResolveParams R) {
+    uint32_t gx, gy;
+    const bool active = tile_pixel(R.frame, gx, gy);
+    uint32_t flags = 0u;
+    if (active) flags = resolve_pixel<true>(R.frame, R.frames, gx, gy, R.rgba, R.albedo, R.normal, &R.aether, R.depth);
+    const unsigned long long valid = __ballot((flags & 1u) != 0u), bad = __ballot((flags & 2u) != 0u);
+    if (threadIdx.x == 0) {
+        if (valid) atomicOr(&R.frame.stats[2], 1u);
+        if (bad) atomicOr(&R.frame.stats[3], 1u);
+    }
+}
+
+// f32 RGB(A) texels into the binary16 drape of a session (f3d_drape.h drape_pack_at): one lane a texel of the window, 256 to a
+// workgroup along the row (the loads and the 8-byte stores of a row are contiguous), grid.y = the window's rows.
+__global__ __launch_bounds__(256) void k_drape_pack(const DrapePackParams B) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x, r = blockIdx.y;
+    if (c < B.cols && r < B.rows) drape_pack_at(B, r, c);
 }
 
 __global__ __launch_bounds__(kWave) void k_ray_batch(const RayBatchParams B) {

@@ -133,6 +133,16 @@ struct f3d_session {
     // DEM visibility rasters (f3d_session_raster, host form): targets and outputs pass through, grown only for a larger call
     void *raster_scratch = nullptr;
     uint64_t raster_bytes = 0;
+    // drape (f3d_session_drape): the buffer params.drape names -- a 64-byte DrapeDev record, then rows x cols binary16 RGBA
+    // texels --, the host's copy of the record, and the slab the f32 rows of a host image pass through (grown only)
+    struct Drape {
+        void *buffer = nullptr;
+        uint64_t bytes = 0;
+        uint32_t rows = 0, cols = 0;
+        DrapeDev record{};
+        float *staging = nullptr;
+        uint64_t staging_bytes = 0;
+    } drape;
     TerrainTables tables;
     uint32_t width = 0, height = 0, row_begin = 0, row_end = 0, rows = 0;
     PackedReservoir *res[2] = {nullptr, nullptr};
@@ -721,6 +731,14 @@ void join_bands(f3d_session &s, bool edges_only = false) {
         }
 }
 
+// The frame paths that have no draped form (the frames in flight and their wavefront form, the two-part frame, the strip
+// batch): what they tell a draped session (f3d_session_drape, f3d_host_drape.h).
+void refuse_draped(const f3d_session &s, const char *path) {
+    if (s.params.drape)
+        fail(F3D_STATUS_VALUE, "%s has no draped form: a draped session renders through the fused frame path (f3d_session_enqueue_frames, "
+             "f3d_session_render); remove the drape first (f3d_session_drape with a null image)", path);
+}
+
 // How many frames to trace at once from `frame` on: 2, 2, 4, 8, ... up to the session's frames in flight.  A pixel whose
 // sun-direction prediction fails is traced again by k_fix inside the ordered chain of merges (~0.17 ms for one pixel of
 // the headline scene) in every remaining frame of its batch, because the prediction only learns from merges; which
@@ -739,6 +757,7 @@ uint32_t trace_batch(const f3d_session &s, uint32_t frame, uint32_t remaining) {
 
 // ---- frames in flight: trace a batch of frames in one launch, then merge them in order ------------------------
 void enqueue_trace(f3d_session &s, uint32_t first, uint32_t count) {
+    refuse_draped(s, s.wavefront ? "the wavefront trace (k_wf_primary / k_wf_occl)" : "a trace batch (k_trace)");
     if (!s.fd_frames) fail(F3D_STATUS_VALUE, "this session has no frames in flight (f3d_session_opts.frames_in_flight)");
     if (count == 0u || count > s.fd_frames) fail(F3D_STATUS_VALUE, "a trace batch holds 1..%u frames (got %u)", s.fd_frames, count);
     FrameParams &P = s.params;
@@ -776,6 +795,7 @@ void enqueue_trace(f3d_session &s, uint32_t first, uint32_t count) {
 }
 
 void enqueue_merge(f3d_session &s, uint32_t frame, bool collect) {
+    refuse_draped(s, "a merge of traced frames (k_merge)");
     if (!s.fd_frames || s.trace_first < 0 || frame < (uint32_t)s.trace_first || frame >= (uint32_t)s.trace_first + s.trace_count)
         fail(F3D_STATUS_VALUE, "frame %u is not in the traced batch [%lld, %lld)", frame, (long long)s.trace_first,
              (long long)s.trace_first + s.trace_count);
@@ -961,6 +981,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 #include "f3d_host_update.h"  // session updates (re-arm, re-aim, re-mesh, re-terrain): one path, their own steps and their C ABI
 #include "f3d_host_query.h"  // ray queries on a live session: checks, scratch, staged copies, launch and their C ABI
 #include "f3d_host_raster.h"  // DEM visibility rasters on a live session: checks, scratch, staged copies, launch and their C ABI
+#include "f3d_host_drape.h"  // an image draped over the terrain of a live session: checks, buffer, staged upload, packing and its C ABI
 
 // ---------------------------------------------------------------------------------------
 // C ABI
@@ -1038,6 +1059,7 @@ int f3d_session_enqueue_frame_part(f3d_session *s, uint32_t frame, uint32_t part
     return c_abi(err, errlen, [&] {
         DeviceGuard g(checked(s).device);
         if (part != 1u && part != 2u) fail(F3D_STATUS_VALUE, "frame part must be 1 (edge rows) or 2 (interior)");
+        refuse_draped(*s, "a frame in two parts (f3d_session_enqueue_frame_part)");
         if (s->fd_frames) fail(F3D_STATUS_VALUE, "sessions with frames in flight are driven by enqueue_trace / enqueue_merge");
         enqueue_frame(*s, frame, collect_stats != 0, part, true);
     });
@@ -1249,6 +1271,12 @@ int f3d_session_fingerprint(f3d_session *s, uint64_t *out, uint32_t count) {
         out[13] = dev(s->res[0], res_n * sizeof(PackedReservoir)) ^ (dev(s->res[1], res_n * sizeof(PackedReservoir)) * 3ull);
         out[14] = dev(P.accum_mean, px * sizeof(float4)) ^ (dev(P.welford_m2, px * sizeof(float)) * 3ull);
         out[15] = dev(P.head, P.head ? px * sizeof(uint2) : 0);
+        // (a caller that asks for a 17th word: the drape -- its record without the device address, and its texels)
+        if (count >= 17u) {
+            DrapeDev rec = s->drape.record;
+            rec.texels = nullptr;
+            out[16] = s->drape.buffer ? hash_bytes(&rec, sizeof(rec), 7) ^ (dev((const char *)s->drape.buffer + sizeof(DrapeDev), (size_t)s->drape.bytes - sizeof(DrapeDev)) * 3ull) : 0ull;
+        }
         return F3D_STATUS_OK;
     } catch (...) {
         return F3D_STATUS_DEVICE;

@@ -121,6 +121,7 @@ void enqueue_halo_sync(f3d_session &s, uint32_t frame) {  // behind the kernels 
 // Frames [first, first + count) of a strip whose neighbours are connected: enqueue_range with the halo step after
 // every frame.
 void enqueue_batch_strip(f3d_session &s, uint32_t first, uint32_t count, bool collect_last) {
+    refuse_draped(s, "a strip batch with peer halos (f3d_session_enqueue_batch_strip)");
     if (!s.halo_flags) fail(F3D_STATUS_VALUE, "f3d_session_halo_export has not been called for this session");
     // The neighbours wait for `counter >= frame + 1` on a counter that is never cleared: frames of a connected session only
     // go up (a second pass over frames 0.. would find the neighbours' counters high already and pull rows of the wrong frame).

@@ -39,6 +39,15 @@ hipError_t launch_head(const FrameParams &p, hipStream_t stream) {  // the band'
     return hipGetLastError();
 }
 
+// Waves per SIMD the draped frame kernels are compiled for -- their own register budget ("Draping an image"):
+// the sampled albedo makes the sun term and the IBL term per-lane values that live across the sun march (the undraped kernel
+// forms them again from render constants).  At 80 VGPRs / 6 waves that costs scratch the undraped kernel does not have (terrain
+// only: 12 against 8 B with 2, 4, 8 sample lanes, 76 against 44 B with one); at 96 VGPRs / 5 waves the 2-, 4- and 8-lane forms
+// have none and the one-lane forms 36 B (terrain only) and 28 B (mesh), below the undraped kernel's 44 and 84.
+#if !defined(F3D_DRAPE_WAVES)  // (6: A/B build, tools/build_variant.sh)
+#define F3D_DRAPE_WAVES 5
+#endif
+constexpr int kDrapeWaves = F3D_DRAPE_WAVES;
 hipError_t launch_frame(const FrameParams &p, int variant, hipStream_t stream) {
     const uint32_t lanes = p.sample_lanes ? p.sample_lanes : 1u;
     if (frame_grid(p, lanes) == 0u) return hipSuccess;  // an empty band
@@ -46,6 +55,29 @@ hipError_t launch_frame(const FrameParams &p, int variant, hipStream_t stream) {
     // (F3D_FORCE_MESH_KERNEL=1: A/B switch, the mesh-capable instantiation for a terrain-only scene -- same results)
     static const bool force_mesh = getenv("F3D_FORCE_MESH_KERNEL") != nullptr;
     const bool mesh = p.mesh.traversal_mode == 0u || force_mesh;
+    if (p.drape) {  // a draped session: the default variant of each sample-lane count (the host refuses the A/B variants)
+        if (variant % 1000 != 0) return hipErrorInvalidValue;
+        switch (lanes) {
+            case 1:
+                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 1, true>), grid, block, 0, stream, p);
+                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 1, false>), grid, block, 0, stream, p);
+                break;
+            case 2:
+                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 2, true>), grid, block, 0, stream, p);
+                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 2, false>), grid, block, 0, stream, p);
+                break;
+            case 4:
+                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 4, true>), grid, block, 0, stream, p);
+                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 4, false>), grid, block, 0, stream, p);
+                break;
+            case 8:
+                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 8, true>), grid, block, 0, stream, p);
+                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 8, false>), grid, block, 0, stream, p);
+                break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     if (lanes != 1u) {  // one wave per workgroup (register-budget A/B variants for 4 and 8 lanes only)
         switch (lanes * 1000 + (uint32_t)(variant % 1000)) {
             case 2000:
@@ -197,7 +229,13 @@ hipError_t launch_reaim(const RearmParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream) {
-    hipLaunchKernelGGL(k_resolve, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);
+    if (p.frame.drape) hipLaunchKernelGGL(k_resolve_drape, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);
+    else hipLaunchKernelGGL(k_resolve, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);
+    return hipGetLastError();
+}
+hipError_t launch_drape_pack(const DrapePackParams &p, hipStream_t stream) {
+    if (p.rows == 0u || p.cols == 0u) return hipSuccess;
+    hipLaunchKernelGGL(k_drape_pack, dim3((p.cols + 255u) / 256u, p.rows), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream) {

@@ -5,6 +5,7 @@
 
 #include "f3d_aether.h"
 #include "f3d_build.h"
+#include "f3d_drape.h"
 #include "f3d_scene.h"
 
 namespace f3d {
@@ -41,7 +42,8 @@ hipError_t launch_tile_order(const FrameParams &p, const uint32_t *cost, uint32_
 hipError_t launch_gbuffer(const FrameParams &p, float4 *gbuffer_n, float *depth, hipStream_t stream);
 hipError_t launch_rearm(const RearmParams &p, hipStream_t stream);  // same grid and pixel mapping as launch_gbuffer
 hipError_t launch_reaim(const RearmParams &p, hipStream_t stream);  // ... and its LDS: the G-buffer pass and the re-arm in one
-hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream);
+hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream);  // (a draped session: the draped resolve)
+hipError_t launch_drape_pack(const DrapePackParams &p, hipStream_t stream);  // f32 texels into a session's binary16 drape (f3d_drape.h)
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream);
 hipError_t launch_query(const QueryParams &p, hipStream_t stream);  // ray queries on a live session (f3d_query.h), 64 rays a workgroup
 hipError_t launch_raster(const RasterParams &p, hipStream_t stream);  // DEM visibility rasters (f3d_raster.h), 64 consecutive samples a workgroup

@@ -196,6 +196,19 @@ struct WfQueues {
 };
 constexpr uint32_t kWfRegion = 64u;
 
+// An image draped over the terrain (f3d_session_drape; f3d_drape.h): the albedo of terrain hits, per texel.  The record lives
+// in DEVICE memory, in front of the texels it names (FrameParams::drape points at it; null: no drape, light.albedo is the
+// terrain's albedo): the frame kernel holds one pointer in scalar registers across its marches, not the record, and reads
+// the record where a hit is shaded.  Only the draped instantiations of the frame kernel and the draped resolve read it.
+struct alignas(16) DrapeDev {
+    const uint2 *texels;  // rows x cols binary16 RGBA: x = r | g << 16, y = b | a << 16
+    uint32_t rows, cols;
+    float scale_x, offset_x, scale_z, offset_z;  // texel coordinate = DEM-sample coordinate * scale + offset
+    uint32_t filter;      // kDrapeNearest / kDrapeBilinear
+    uint32_t reserved[7];
+};
+static_assert(sizeof(DrapeDev) == 64, "the drape's record is the 64-byte header of its buffer");
+
 // Per-frame kernel parameters.
 struct FrameParams {
     TerrainDev terrain;
@@ -236,6 +249,7 @@ struct FrameParams {
     uint32_t *fix_list;   // (unused since round 4: round 3 listed the pixels for a second kernel)
     uint32_t *fix_count;  // [2]: running total (diagnostics)
     WfQueues wf;          // wavefront form of the trace batch (sun_o == null: k_trace traces the rays itself)
+    const DrapeDev *drape;  // per-texel terrain albedo (null: none); read by the draped kernels only
 };
 
 // Re-arm / re-aim of a live session (f3d_session_rearm, f3d_session_reaim; k_rearm, k_reaim): frame = the new uniforms

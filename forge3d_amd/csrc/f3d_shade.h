@@ -14,6 +14,7 @@
 #pragma once
 
 #include "f3d_aether.h"
+#include "f3d_drape.h"
 #include "f3d_march.h"
 #include "f3d_trace.h"
 
@@ -756,6 +757,9 @@ struct ShadeSetup {
 
 // Everything of a sample's shading except the two occlusion rays; draws u1, u2 from `rng` on a hit; o.a = the miss
 // radiance on a miss, o.target_pdf = the candidate weight.
+// DRAPE: the albedo of a terrain hit is the session's drape at the hit point (f3d_drape.h) instead of light.albedo -- sampled
+// here, once per primary hit; it is dead once target_pdf, su.y and q.b0 are formed and never crosses a march.
+template <bool DRAPE = false>
 F3D_HD ShadeSetup sample_shade_setup(const FrameParams &P, bool prev_valid, const PrimaryHit &ph, uint32_t &rng, SampleOut &o) {
     ShadeSetup su;
     IblRay &q = su.q;
@@ -772,11 +776,17 @@ F3D_HD ShadeSetup sample_shade_setup(const FrameParams &P, bool prev_valid, cons
         return su;
     }
     const V3 n = ph.hit.n;
-    V3 albedo = P.light.albedo;
-    F3D_OPAQUE_UNIFORM(albedo.x);  // (render constants: their products are formed per sample, not held across the kernel)
-    F3D_OPAQUE_UNIFORM(albedo.y);
-    F3D_OPAQUE_UNIFORM(albedo.z);
-    if (ph.hit.kind != 1u) albedo = V3{0.7f, 0.7f, 0.8f};
+    V3 albedo;
+    if constexpr (DRAPE) {
+        albedo = V3{0.7f, 0.7f, 0.8f};
+        if (ph.hit.kind == 1u) albedo = drape_sample(*P.drape, P.terrain, ph.hit.p.x, ph.hit.p.z);
+    } else {
+        albedo = P.light.albedo;
+        F3D_OPAQUE_UNIFORM(albedo.x);  // (render constants: their products are formed per sample, not held across the kernel)
+        F3D_OPAQUE_UNIFORM(albedo.y);
+        F3D_OPAQUE_UNIFORM(albedo.z);
+        if (ph.hit.kind != 1u) albedo = V3{0.7f, 0.7f, 0.8f};
+    }
     const V3 so = along(ph.hit.p, 1e-3f, n);
     // candidate generation for this hit (:500-512)
     o.target_pdf = luminance((albedo * P.light.color) * f_max(dot(n, P.light.wi), 0.0f));
@@ -810,10 +820,10 @@ F3D_HD ShadeSetup sample_shade_setup(const FrameParams &P, bool prev_valid, cons
 // (with its shadow ray), and the IBL ray to trace; draws u1, u2 from `rng` on a hit.
 // reuse_w(): the reuse weight of the frame head, asked for AFTER the shadow ray (the sample-lane kernels keep it in the
 // lane's LDS column, f3d_frame.h, instead of in a register across the march).
-template <class Pending, class ReuseW>
+template <bool DRAPE = false, class Pending, class ReuseW>
 F3D_HD IblRay sample_shade_sun(const FrameParams &P, bool prev_valid, ReuseW reuse_w, const PrimaryHit &ph, uint32_t &rng,
                                SampleOut &o, Pending &pend) {
-    const ShadeSetup su = sample_shade_setup(P, prev_valid, ph, rng, o);
+    const ShadeSetup su = sample_shade_setup<DRAPE>(P, prev_valid, ph, rng, o);
     if (su.need_sun) {
         float vis = 1.0f;
 #if defined(F3D_MODEL_HINT_SUN)  // scheduling-model builds of the emulator only
@@ -834,11 +844,11 @@ F3D_HD IblRay sample_shade_sun(const FrameParams &P, bool prev_valid, ReuseW reu
 #endif
     return su.q;
 }
-template <class Pending>
+template <bool DRAPE = false, class Pending>
 F3D_HD IblRay sample_shade_sun(const FrameParams &P, const FrameHead &h, const PrimaryHit &ph, uint32_t &rng,
                                SampleOut &o, Pending &pend) {
     const float w = h.reuse_w;
-    return sample_shade_sun(P, h.prev_valid, [w]() F3D_LAMBDA { return w; }, ph, rng, o, pend);
+    return sample_shade_sun<DRAPE>(P, h.prev_valid, [w]() F3D_LAMBDA { return w; }, ph, rng, o, pend);
 }
 
 // The verdict of an IBL ray (intersect_ibl_occlusion_ray, hybrid_traversal.wgsl:250-259).
@@ -852,11 +862,11 @@ F3D_HD bool ibl_occluded(const FrameParams &P, V3 o, V3 d, Pending &pend, float 
 }
 
 // Shading of one sample on one lane: both halves back to back.
-template <class Pending>
+template <bool DRAPE = false, class Pending>
 F3D_HD SampleOut sample_shade(const FrameParams &P, const FrameHead &h, const PrimaryHit &ph, uint32_t &rng,
                               Pending &pend) {
     SampleOut o;
-    const IblRay q = sample_shade_sun(P, h, ph, rng, o, pend);
+    const IblRay q = sample_shade_sun<DRAPE>(P, h, ph, rng, o, pend);
     if (q.valid) o.b = q.b0 * (ibl_occluded(P, q.o, q.d, pend, q.t_stop) ? 0.0f : 1.0f);
     return o;
 }
@@ -1019,7 +1029,7 @@ F3D_HD float fix_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, const flo
 // one sample after the other on one lane.
 // (A per-lane ray state machine with ballot-gated shading transitions was measured at 0.5-0.7x of
 // this nested form on MI355X and removed -- profiles/README.md.)
-template <class Pending>
+template <bool DRAPE = false, class Pending>
 F3D_HD float frame_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, Pending &pend) {
     const FrameHead h = frame_head(P, gx, gy);
     uint32_t rng = h.rng;
@@ -1028,7 +1038,7 @@ F3D_HD float frame_pixel(const FrameParams &P, uint32_t gx, uint32_t gy, Pending
     for (uint32_t s = 0u; s < P.spp; s++) {
         const PrimaryHit ph = sample_primary(P, gx, gy, rng, pend);
         rng = ph.rng;
-        const SampleOut o = sample_shade(P, h, ph, rng, pend);
+        const SampleOut o = sample_shade<DRAPE>(P, h, ph, rng, pend);
         accumulate_sample(cand, radiance, o.a, o.b, o.target_pdf);
     }
     return frame_tail(P, gx, gy, cand, radiance);
@@ -1133,6 +1143,10 @@ F3D_HD void reaim_pixel(const RearmParams &R, uint32_t gx, uint32_t gy, Pending 
 // Reinhard -> RGBA16F -> u8 (hybrid_kernel.wgsl:109-112, render_terrain.rs:1358-1366),
 // AOVs through RGBA16F (render_terrain.rs:438-447, :1367-1393). flags: bit0 valid, bit1 bad.
 // aether != null && aether->enabled: the AETHER aerial-perspective post (f3d_aether.h) replaces the plain Reinhard.
+// DRAPE (needs depth): the albedo AOV of a terrain pixel is the session's drape at the centre ray's hit point, formed again
+// as closest_hit left it -- along(cam.origin, t, d) with the depth AOV's t (rearm_certificate): the point a pixel query
+// reports.
+template <bool DRAPE = false>
 F3D_HD uint32_t resolve_pixel(const FrameParams &P, uint32_t frames, uint32_t gx, uint32_t gy, uint8_t *rgba,
                               float *albedo, float *normal, const AetherDev *aether = nullptr,
                               const float *depth = nullptr) {
@@ -1174,7 +1188,13 @@ F3D_HD uint32_t resolve_pixel(const FrameParams &P, uint32_t frames, uint32_t gx
     rgba[4 * lp + 3] = 255;
 
     const uint32_t kind = (uint32_t)g.w;
-    const V3 a = kind == 1u ? P.light.albedo : (kind == 2u ? V3{0.7f, 0.7f, 0.8f} : V3{0.0f, 0.0f, 0.0f});
+    V3 a = kind == 1u ? P.light.albedo : (kind == 2u ? V3{0.7f, 0.7f, 0.8f} : V3{0.0f, 0.0f, 0.0f});
+    if constexpr (DRAPE) {
+        if (kind == 1u) {
+            const V3 p = along(P.cam.origin, depth[lp], camera_dir(P.cam, gx, gy, 0.0f, 0.0f));
+            a = drape_sample(*P.drape, P.terrain, p.x, p.z);
+        }
+    }
     const V3 n = kind != 0u ? V3{g.x, g.y, g.z} : V3{0.0f, 0.0f, 0.0f};
     albedo[3 * lp + 0] = round_to_half(a.x);
     albedo[3 * lp + 1] = round_to_half(a.y);

@@ -190,6 +190,119 @@ class TerrainSession:
         else:
             self._terrain_top = max(self._terrain_top, float(block.max()) * self._exaggeration)
 
+    # -- drape: an image laid over the terrain, per-texel albedo -----------------------------------
+    DRAPE_FILTERS = {"nearest": _native.DRAPE_NEAREST, "bilinear": _native.DRAPE_BILINEAR}
+
+    def drape_registration(self, rows: int, cols: int, registration="area"):
+        """The four f32 numbers ``(scale_x, offset_x, scale_z, offset_z)`` that take DEM-sample coordinates to texel coordinates
+        (``t = f * scale + offset``) for an image of ``rows x cols`` texels: ``"area"`` -- the image covers the DEM's extent edge
+        to edge, ``scale = cols / (w - 1)``, ``offset = -0.5``; ``"point"`` -- texel centres sit on the corresponding fraction of
+        samples, ``scale = (cols - 1) / (w - 1)``, ``offset = 0``; or four numbers of the caller's, taken as given."""
+        dem_h, dem_w = self.dem_shape
+        if isinstance(registration, str):
+            if registration == "area":
+                reg = (cols / (dem_w - 1), -0.5, rows / (dem_h - 1), -0.5)
+            elif registration == "point":
+                reg = ((cols - 1) / (dem_w - 1), 0.0, (rows - 1) / (dem_h - 1), 0.0)
+            else:
+                raise ValueError(f"registration must be 'area', 'point' or (scale_x, offset_x, scale_z, offset_z), got {registration!r}")
+        else:
+            reg = tuple(float(v) for v in registration)
+            if len(reg) != 4:
+                raise ValueError(f"registration must be 'area', 'point' or (scale_x, offset_x, scale_z, offset_z), got {registration!r}")
+        reg = tuple(np.float32(v) for v in reg)
+        if not all(np.isfinite(v) for v in reg) or reg[0] == 0 or reg[2] == 0:
+            raise ValueError(f"registration numbers must be finite and the scales non-zero, got {tuple(float(v) for v in reg)} "
+                             "(a one-texel image under 'point' has no extent: use 'area')")
+        return reg
+
+    def drape(self, image, camera=None, *, filter="bilinear", registration="area", at=None, srgb=False, wait=True, **rearmable):
+        """reaim() under an image laid over the terrain: the albedo of terrain hits becomes the image's texel under the hit point
+        (mesh hits keep theirs, the sky is untouched), per sample, and the albedo AOV the image at the centre ray's hit.
+        ``image`` is ``(H, W, 3|4)`` linear RGB reflectances (a fourth channel is ignored), row 0 on DEM row 0 and column 0 on
+        DEM column 0 -- the heightmap's orientation: a NumPy float32 array, a uint8 array (divided by 255), a float32 tensor
+        on the session's device (nothing copied; ``wait=False`` returns with the packing kernel in flight on the session's
+        stream), or ``None``, which removes the drape -- every later output is then bit-identical to a session that never had
+        one.  ``srgb=True`` decodes a NumPy image to linear first.  ``filter``: ``"bilinear"`` (clamp to edge) or ``"nearest"``.
+        ``registration``: see drape_registration().  ``at=(row, col)`` overwrites that window of the session's drape with
+        ``image`` (a time-lapse of imagery without uploading all of it again): size, filter and registration stay.
+        Texels are stored as binary16; a host image with a non-finite, negative or > 65504 value is refused, a tensor's such
+        values are stored as 0.  ``camera`` None keeps the current one (and the current exposure); otherwise it is read as
+        reaim() reads it.  Same contract as reaim(): the render restarts at frame 0 and a refused value leaves the session as
+        it was, rendering the old drape.  Frames in flight, the register-budget A/B kernel variants and connected peer halos
+        have no draped form: such a session refuses a drape."""
+        self._known("drape", rearmable)
+        q = _native.DrapeDesc()
+        q.struct_size = C.sizeof(_native.DrapeDesc)
+        keep = None
+        if image is None:
+            if at is not None:
+                raise ValueError("image=None removes the drape: it takes no at=(row, col)")
+        else:
+            if filter not in self.DRAPE_FILTERS:
+                raise ValueError(f"filter must be 'nearest' or 'bilinear', got {filter!r}")
+            if type(image).__module__.split(".")[0] == "torch":
+                import torch  # (only for callers who hand tensors in)
+
+                if not image.is_cuda:
+                    raise ValueError("a tensor drape needs a tensor on the session's device (NumPy arrays take the host form)")
+                if image.dtype != torch.float32:
+                    raise ValueError(f"a tensor drape must be float32, got {image.dtype}")
+                if srgb:
+                    raise ValueError("srgb=True decodes a NumPy image: decode a tensor before handing it in")
+                if image.ndim != 3 or image.shape[2] not in (3, 4):
+                    raise ValueError(f"image must have shape (H, W, 3) or (H, W, 4), got {tuple(image.shape)}")
+                if not wait and not image.is_contiguous():
+                    raise ValueError("wait=False needs a contiguous tensor: the packing kernel reads the caller's memory after the call "
+                                     "returns, and a copy made here would be gone by then")
+                keep = image.contiguous()
+                shape = tuple(int(v) for v in keep.shape)
+                q.image = keep.data_ptr() if keep.numel() else None
+                q.flags = _native.DRAPE_DEVICE_POINTERS | (0 if wait else _native.DRAPE_NO_WAIT)
+            else:
+                arr = np.asarray(image)
+                if arr.ndim != 3 or arr.shape[2] not in (3, 4):
+                    raise ValueError(f"image must have shape (H, W, 3) or (H, W, 4), got {arr.shape}")
+                if arr.dtype == np.uint8:
+                    arr = arr.astype(np.float32) / np.float32(255.0)
+                elif arr.dtype != np.float32:
+                    raise ValueError(f"image must be float32 or uint8, got {arr.dtype}")
+                if srgb:
+                    arr = srgb_to_linear(arr)
+                if not wait:
+                    raise ValueError("wait=False is for tensor images: an image in host memory has been read when the call returns")
+                keep = np.ascontiguousarray(arr, dtype=np.float32)
+                shape = keep.shape
+                q.image = keep.ctypes.data if keep.size else None
+            if shape[0] == 0 or shape[1] == 0:
+                raise ValueError(f"image is empty: shape {shape}")
+            q.rows, q.cols, q.channels = shape
+            if at is None:
+                q.filter = self.DRAPE_FILTERS[filter]
+                q.scale_x, q.offset_x, q.scale_z, q.offset_z = self.drape_registration(shape[0], shape[1], registration)
+            else:
+                row, col = (int(v) for v in at)
+                if row < 0 or col < 0:
+                    raise ValueError(f"at=(row, col) must not be negative, got {tuple(at)}")
+                q.at_row, q.at_col = row, col
+                q.flags |= _native.DRAPE_PATCH
+        q.aim = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_drape, q, q.aim.arm, camera)  # (keep lives until here)
+        del keep
+
+    @property
+    def draped(self) -> bool:
+        """Does the session hold a drape?"""
+        return bool(self._lib.f3d_session_draped(self._handle, None))
+
+    def drape_info(self):
+        """``None`` without a drape, else ``{"rows", "cols", "filter", "bytes"}`` of the one the session holds."""
+        info = (C.c_uint32 * 4)()
+        if not self._lib.f3d_session_draped(self._handle, info):
+            return None
+        names = {v: k for k, v in self.DRAPE_FILTERS.items()}
+        return {"rows": int(info[0]), "cols": int(info[1]), "filter": names[int(info[2])], "bytes": int(info[3])}
+
     # what the four updates share: the keyword check, the camera rule, the call with what the wrapper remembers of it
     def _known(self, method: str, rearmable: dict) -> None:
         unknown = [k for k in rearmable if k not in self.REARMABLE]
@@ -524,12 +637,12 @@ class TerrainSession:
 
     FINGERPRINT_FIELDS = ("camera", "light", "terrain_scalars", "mesh_scalars", "scalars", "leaf_table", "band_tables",
                           "mesh_vertices", "mesh_indices", "bvh_nodes", "bvh_triangles", "environment", "gbuffer",
-                          "reservoirs", "accumulation", "frame_heads")
+                          "reservoirs", "accumulation", "frame_heads", "drape")
 
     def fingerprint(self) -> dict:
         """Diagnostics (synchronises): hashes of everything a frame launch reads, by name."""
-        out = (C.c_uint64 * 16)()
-        if self._lib.f3d_session_fingerprint(self._handle, out, 16) != 0:
+        out = (C.c_uint64 * 17)()
+        if self._lib.f3d_session_fingerprint(self._handle, out, 17) != 0:
             raise RuntimeError("f3d_session_fingerprint failed")
         return dict(zip(self.FINGERPRINT_FIELDS, (int(v) for v in out)))
 
@@ -697,6 +810,17 @@ class TerrainSession:
         if rc != 0:
             raise RuntimeError("kernel timing failed")
         return float(avg.value), int(n.value)
+
+
+def srgb_to_linear(image) -> np.ndarray:
+    """The sRGB transfer function's inverse on the first three channels of a float32 image in [0, 1], in float32."""
+    out = np.array(image, dtype=np.float32, copy=True)
+    c = out[..., :3]
+    low = c <= np.float32(0.04045)
+    with np.errstate(invalid="ignore"):
+        high = np.power((c + np.float32(0.055)) / np.float32(1.055), np.float32(2.4), dtype=np.float32)
+    out[..., :3] = np.where(low, c / np.float32(12.92), high)
+    return out
 
 
 def kernel_variant(*, sample_lanes: int = 0, waves_per_simd: int = 0, tile_map: int = 0, leaf_quorum: int = 0, share_below: int = 0) -> int:

@@ -8,8 +8,8 @@ offline render: ``open_viewer_async(width, height, terrain_path=..., fov_deg=...
 ``load_terrain``, ``set_orbit_camera``, ``set_camera_lookat``, ``set_fov``, ``set_sun``, ``set_sun_time``, ``set_ibl``,
 ``set_z_scale``, ``snapshot(path, width, height)``, ``render_animation``, ``get_stats``, ``close`` and the context
 manager.  There is no subprocess and no window: every snapshot is a converged path-traced frame on the MI355X.
-Commands of the raster viewer that have no meaning offline (labels, picking, overlays, point clouds) raise
-``ViewerError`` instead of being ignored.
+``load_overlay`` drapes ONE image over the terrain as its per-texel albedo (TerrainSession.drape).  Commands of the raster
+viewer that have no meaning offline (labels, vector overlays, point clouds) raise ``ViewerError`` instead of being ignored.
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ class ViewerError(Exception):
     """reference python/forge3d/viewer.py:160-162"""
 
 
-_RASTER_ONLY = ("load_obj", "load_gltf", "load_bundle", "load_overlay", "load_point_cloud", "set_point_cloud_params",
+_RASTER_ONLY = ("load_obj", "load_gltf", "load_bundle", "load_point_cloud", "set_point_cloud_params",
                 "set_transform", "add_label", "add_labels", "add_line_label", "add_curved_label", "add_callout",
                 "add_vector_overlay", "set_labels_enabled", "clear_labels", "remove_label", "set_label_typography",
                 "set_declutter_algorithm", "poll_pick_events", "update_labels", "load_label_atlas",
@@ -44,6 +44,7 @@ class ViewerHandle(OfflineTerrainViewer):
         self._sun_intensity = 2.5
         self._revision = 0
         self._open = True
+        self._overlay = None
 
     # -- scene --------------------------------------------------------------------------------------------
     def load_terrain(self, path: Union[str, Path, np.ndarray], spacing: Union[float, Tuple[float, float], None] = None) -> None:
@@ -88,6 +89,90 @@ class ViewerHandle(OfflineTerrainViewer):
         self._env, self._env_intensity = env, float(intensity)
         self._revision += 1
 
+    def load_overlay(self, name: str, path: Union[str, Path, np.ndarray], extent: Optional[Sequence[float]] = None,
+                     opacity: Optional[float] = None, z_order: Optional[int] = None, preserve_colors: Optional[bool] = None, *,
+                     filter: str = "bilinear", srgb: Optional[bool] = None) -> None:
+        """reference viewer.py:1009-1042, as far as a path tracer has a counterpart: the image becomes the terrain's albedo
+        (the viewer keeps no session between renders: every later render() / snapshot() creates its session, drapes it with
+        this image through TerrainSession.drape and renders; render_animation() drapes ONE session and re-aims it per key), lit
+        and shadowed like the ground it lies on.  ``path``: an 8-bit PNG (read by forge3d_amd.io), a .npy file, or an ``(H, W, 3|4)`` array -- uint8 or
+        float32; row 0 lies on DEM row 0.  ``extent`` is the reference's normalised ``(u0, v0, u1, v1)`` of the DEM's footprint
+        the image covers (u along DEM columns, v along DEM rows; default the whole DEM); outside it the image's edge texels
+        continue (clamp to edge).  ``srgb``: decode to linear first (default: yes for files and uint8 arrays, no for float32).
+        ONE overlay at a time: loading another replaces it whatever its name.  ``opacity``, ``z_order`` and
+        ``preserve_colors`` belong to the raster viewer's compositor and are refused when given."""
+        for key, value in (("opacity", opacity), ("z_order", z_order), ("preserve_colors", preserve_colors)):
+            if value is not None:
+                raise ViewerError(f"ViewerHandle.load_overlay({key}=...) belongs to the interactive raster viewer's compositor; the "
+                                  "offline path tracer drapes the image as the terrain's albedo and has no counterpart")
+        if filter not in ("nearest", "bilinear"):
+            raise ViewerError(f"overlay filter must be 'nearest' or 'bilinear', got {filter!r}")
+        if isinstance(path, np.ndarray):
+            image, from_file = path, False
+        elif Path(path).suffix.lower() == ".png":
+            try:
+                image, from_file = _io.png_to_numpy(path), True
+            except (OSError, ValueError) as exc:
+                raise ViewerError(str(exc)) from exc
+        elif Path(path).suffix.lower() == ".npy":
+            image, from_file = np.load(Path(path)), True
+        else:
+            raise ViewerError(f"Unsupported overlay format '{Path(path).suffix}' for '{path}': expected .png or .npy")
+        if image.ndim == 2:
+            image = np.repeat(image[:, :, None], 3, 2)
+        elif image.ndim == 3 and image.shape[2] == 2:  # grey + alpha
+            image = np.repeat(image[:, :, :1], 3, 2)
+        if image.ndim != 3 or image.shape[2] not in (3, 4) or image.dtype not in (np.uint8, np.float32):
+            raise ViewerError(f"overlay must be (H, W, 3|4) uint8 or float32, got {image.dtype} {image.shape}")
+        if extent is None:
+            extent = (0.0, 0.0, 1.0, 1.0)
+        u0, v0, u1, v1 = (float(v) for v in extent)
+        if not (np.isfinite([u0, v0, u1, v1]).all() and u1 > u0 and v1 > v0):
+            raise ViewerError(f"overlay extent must be finite (u0, v0, u1, v1) with u1 > u0 and v1 > v0, got {tuple(extent)}")
+        decode = (from_file or image.dtype == np.uint8) if srgb is None else bool(srgb)
+        self._overlay = {"name": str(name), "image": np.ascontiguousarray(image), "extent": (u0, v0, u1, v1), "filter": filter,
+                         "srgb": decode}
+        self._revision += 1
+
+    def remove_overlay(self, name: str) -> None:
+        """Take the overlay ``name`` off again (reference viewer.py remove_overlay)."""
+        if getattr(self, "_overlay", None) is None or self._overlay["name"] != str(name):
+            raise ViewerError(f"no overlay named {name!r}")
+        self._overlay = None
+        self._revision += 1
+
+    @staticmethod
+    def overlay_registration(dem_shape, image_shape, extent):
+        """(scale_x, offset_x, scale_z, offset_z) of TerrainSession.drape for an image that covers the normalised extent
+        (u0, v0, u1, v1) of the DEM edge to edge: t = ((f / (n - 1)) - u0) / (u1 - u0) * texels - 0.5."""
+        (dem_h, dem_w), (rows, cols), (u0, v0, u1, v1) = dem_shape, image_shape[:2], extent
+        return (cols / ((dem_w - 1) * (u1 - u0)), -u0 * cols / (u1 - u0) - 0.5,
+                rows / ((dem_h - 1) * (v1 - v0)), -v0 * rows / (v1 - v0) - 0.5)
+
+    def render(self, width: Optional[int] = None, height: Optional[int] = None) -> dict:
+        """OfflineTerrainViewer.render; with an overlay loaded, the same loop on a session draped with it."""
+        overlay = getattr(self, "_overlay", None)
+        if overlay is None:
+            return super().render(width, height)
+        dem, w, h, camera, keywords = self._call(width, height)
+        with self._draped_session(dem, w, h, camera, keywords) as s:
+            self.last_result = s.render()
+        return self.last_result
+
+    def _draped_session(self, dem, w, h, camera, keywords):
+        """A session of the viewer's scene, draped with the loaded overlay."""
+        from .session import TerrainSession
+
+        overlay = self._overlay
+        s = TerrainSession(dem, w, h, camera, **keywords)
+        try:
+            reg = self.overlay_registration(s.dem_shape, overlay["image"].shape, overlay["extent"])
+            s.drape(overlay["image"], filter=overlay["filter"], registration=reg, srgb=overlay["srgb"])
+        except Exception:
+            s.close()
+            raise
+        return s
+
     # -- output -------------------------------------------------------------------------------------------
     def _call(self, width: Optional[int] = None, height: Optional[int] = None):
         if not self._open:
@@ -105,6 +190,24 @@ class ViewerHandle(OfflineTerrainViewer):
 
         out = Path(output_dir)
         out.mkdir(parents=True, exist_ok=True)
+        if self._overlay is not None:  # (a draped scene: ONE session draped with the overlay, re-aimed per key)
+            session = None
+            try:
+                for i, key in enumerate(animation):
+                    self.set_orbit_camera(key["phi_deg"], key["theta_deg"], key["radius"], key.get("fov_deg"), key.get("target"))
+                    dem, w, h, camera, keywords = self._call(width, height)
+                    if session is None:
+                        session = self._draped_session(dem, w, h, camera, keywords)
+                    else:
+                        session.reaim(camera)
+                    self.last_result = session.render()
+                    _io.numpy_to_png(out / f"frame_{i:04d}.png", self.last_result["rgba"])
+                    if progress_callback:
+                        progress_callback(i, len(animation))
+            finally:
+                if session is not None:
+                    session.close()
+            return
         frames, call = [], None
         for key in animation:
             self.set_orbit_camera(key["phi_deg"], key["theta_deg"], key["radius"], key.get("fov_deg"), key.get("target"))

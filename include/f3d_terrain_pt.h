@@ -522,6 +522,71 @@ typedef struct f3d_session_raster_desc {
     uint32_t *count;       /* rows * cols, or NULL */
 } f3d_session_raster_desc;
 int f3d_session_raster(f3d_session *session, const f3d_session_raster_desc *desc, char *err, size_t errlen);
+/* ---- drape: an image laid over the terrain, per-texel albedo ---------------------------------------------------------------
+ * What an image changes on top of a re-aim, still without a new session: the albedo of TERRAIN hits.  The drape is
+ * image[rows][cols] of linear RGB reflectances, f32, row-major, `channels` (3 or 4; a fourth channel is ignored) values a
+ * texel; image row 0 lies on DEM row 0 and image column 0 on DEM column 0 -- the heightmap's own orientation.  It replaces
+ * f3d_terrain_ref_desc.albedo for terrain hits only: mesh hits keep (0.7, 0.7, 0.8), the sky is untouched.  All arithmetic
+ * is f32, one rounding per operation.  A terrain hit at world (x, z) has the DEM-sample coordinates
+ *     fx = (x - origin_x) / spacing_x, fz = (z - origin_z) / spacing_z        (origin: -(dem - 1) * spacing / 2, as everywhere)
+ * and the texel coordinates tx = fx * scale_x + offset_x, tz = fz * scale_z + offset_z (finite numbers, scales non-zero; an
+ * image that covers the DEM's extent edge to edge: scale = cols / (dem_width - 1), offset = -0.5; texel centres on the
+ * corresponding fraction of samples: scale = (cols - 1) / (dem_width - 1), offset = 0).
+ *   F3D_DRAPE_NEAREST   texel clamp(floor(t + 0.5), 0, n - 1) per axis
+ *   F3D_DRAPE_BILINEAR  clamp to edge: i0 = floor(t), f = t - i0, taps clamp(i0), clamp(i0 + 1); every lerp is a + f * (b - a),
+ *                       along x first, then along z -- a constant image samples to exactly that constant
+ * Texels are stored as binary16 RGBA (8 bytes, rounded to nearest even as the RGBA16F AOVs are) in a buffer of the session:
+ * rows * cols * 8 bytes, tracked in gpu_resource_bytes and checked against memory_budget_bytes (too small: status 2, the old
+ * drape stays).  The frames sample it once per primary hit -- candidate weight, sun term and IBL term all take the sampled
+ * albedo -- in a draped instantiation of the fused frame kernel; the albedo AOV of a terrain pixel is the drape at the centre
+ * ray's hit point (the position f3d_session_query mode 2 reports for the pixel), rounded to half as before.
+ *   image == NULL            removes the drape: every later output is bit-identical to a session that never had one
+ *   F3D_DRAPE_PATCH          image overwrites the window rows [at_row, at_row + rows) x columns [at_col, at_col + cols) of the
+ *                            session's drape (a time-lapse of imagery without uploading all of it again): the drape keeps its
+ *                            size, filter and registration (the descriptor's are not read).  Refused (status 1) without a drape
+ *                            or when the window does not fit
+ *   host pointers (default)  the texels are looked at first: a non-finite, negative or > 65504 value in a read channel is
+ *                            refused (status 3, "drape texels must be finite and >= 0 ...").  They go up through the pinned
+ *                            staging pair in stream order, a slab of rows at a time via a scratch buffer of the session (at most
+ *                            8 MiB or one row, grown only for a wider row than any before, tracked and budgeted), and k_drape_pack
+ *                            rounds them into the drape.  The call returns once the image has been read; it does not wait
+ *                            for the device
+ *   F3D_DRAPE_DEVICE_POINTERS image is device memory; nothing is copied and nobody can look: k_drape_pack stores a value
+ *                            that is non-finite, negative or > 65504 as 0.  The call returns when the kernel has finished, or
+ *                            -- F3D_DRAPE_NO_WAIT, with DEVICE_POINTERS only -- with it in flight: the caller orders by the
+ *                            stream the session was created on and keeps the image alive until the kernel has read it
+ * An update like re-arm / re-aim / re-mesh / re-terrain: `aim` carries the camera and everything a re-arm takes, the render
+ * restarts at frame 0, everything is validated by the create's code with its messages, every refusal comes before the first
+ * change of the session, and all of it is enqueued on the session stream behind everything enqueued so far.  The next frames
+ * render exactly what a new session draped the same way renders.  A drape survives the other four updates.
+ * Refused with status 1: another struct_size, an unknown flag or filter, channels other than 3 or 4, an empty image or one
+ * above 16384 texels a side, a non-finite registration number or a zero scale, NO_WAIT without DEVICE_POINTERS, connected
+ * peer halos, a session with frames in flight, a register-budget A/B kernel variant (104, 4105).  A draped session renders
+ * through the fused frame path (f3d_session_enqueue_frames, f3d_session_render): f3d_session_enqueue_trace / _merge,
+ * _enqueue_frame_part and _enqueue_batch_strip refuse it (status 1).  No ABI version bump: detected by the symbol
+ * f3d_session_drape. */
+#define F3D_DRAPE_NEAREST 0u
+#define F3D_DRAPE_BILINEAR 1u
+#define F3D_DRAPE_DEVICE_POINTERS 4u
+#define F3D_DRAPE_NO_WAIT 8u
+#define F3D_DRAPE_PATCH 16u
+#define F3D_DRAPE_MAX_SIDE 16384u
+typedef struct f3d_session_drape_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_drape_desc) of the caller's header */
+    uint32_t flags;              /* F3D_DRAPE_DEVICE_POINTERS | _NO_WAIT | _PATCH */
+    const float *image;          /* rows x cols x channels f32, row-major; NULL removes the drape; read during the call only
+                                    (NO_WAIT: until the kernel has run) */
+    uint32_t rows, cols;         /* of the image (PATCH: of the window) */
+    uint32_t channels;           /* 3 or 4 */
+    uint32_t filter;             /* F3D_DRAPE_NEAREST / _BILINEAR */
+    float scale_x, offset_x;     /* tx = fx * scale_x + offset_x */
+    float scale_z, offset_z;     /* tz = fz * scale_z + offset_z */
+    uint32_t at_row, at_col;     /* PATCH: the window's first texel in the session's drape; otherwise 0 */
+    f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
+} f3d_session_drape_desc;
+int f3d_session_drape(f3d_session *session, const f3d_session_drape_desc *desc, char *err, size_t errlen);
+/* Is the session draped?  info (may be NULL) = {rows, cols, filter, bytes of the drape buffer}; returns 1 / 0 (no session: 0). */
+int f3d_session_draped(f3d_session *session, uint32_t info[4]);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);
@@ -551,7 +616,9 @@ uint32_t f3d_halo_rows(void);
 /* Diagnostics: out[0..15] = hashes of everything a frame launch of this session reads.  [0] camera, [1] light,
  * [2] terrain scalars, [3] mesh scalars, [4] other scalars, [5] leaf table, [6] band tables, [7] mesh vertices,
  * [8] mesh indices, [9] BVH nodes, [10] BVH triangles, [11] environment, [12] G-buffer, [13] reservoirs,
- * [14] accumulation + Welford, [15] frame-head records.  Synchronises the session.  count >= 16. */
+ * [14] accumulation + Welford, [15] frame-head records.  Synchronises the session.  count >= 16.  A caller that passes
+ * count >= 17 also gets [16] the drape (f3d_session_drape: its record without the device address, and its texels; 0 without
+ * a drape); a caller that passes 16 is written 16 words as before. */
 int f3d_session_fingerprint(f3d_session *session, uint64_t *out, uint32_t count);
 
 /* Diagnostics (no ABI version bump: detected by the symbol): the mesh BVH this session's frame launches walk, read back from
