@@ -15,63 +15,22 @@
 #include "f3d_query.h"
 #include "f3d_raster.h"
 #include "f3d_lds.h"
+#include "f3d_tiles.h"
 
 namespace f3d {
 
-constexpr int kNumXcd = 8;
-
-// Pixel tile of a wave with S sample lanes per pixel: 64 / S pixels, TW x TH.
-template <uint32_t S>
-struct TileShape {
-    static constexpr uint32_t kLogS = S == 1u ? 0u : (S == 2u ? 1u : (S == 4u ? 2u : 3u));
-#if defined(F3D_TILE_LOGW_S4)  // A/B of the tile shape (profiles/README.md)
-    static constexpr uint32_t kLogW = S <= 2u ? 3u : (S == 4u ? F3D_TILE_LOGW_S4 : 2u);
-#else
-    static constexpr uint32_t kLogW = S <= 2u ? 3u : 2u;      // 8, 8, 4, 4 pixels wide
-#endif
-    static constexpr uint32_t kLogH = 6u - kLogS - kLogW;     // 8, 4, 4, 2 pixels high
-};
-
 // Pixel of this lane: the launch covers the image rows [band_begin, band_end) of the strip, tiled from band_begin.
-// `tile` returns the tile id of the wave (0xFFFFFFFF: the workgroup is padding).
+// `tile` returns the tile id of the wave (kNoTile: the workgroup is padding).  The geometry is f3d_tiles.h's.
 // wg: the workgroup's position in the dispatch order of ONE frame (blockIdx.x, except in k_trace's batches: batch_slot).
 template <uint32_t S = 1u>
 __device__ __forceinline__ bool tile_pixel(const FrameParams &P, uint32_t &gx, uint32_t &gy, uint32_t &tile,
                                            const uint32_t *order = nullptr, uint32_t wg = 0xFFFFFFFFu) {
     if (wg == 0xFFFFFFFFu) wg = blockIdx.x;
-    using Shape = TileShape<S>;
-    constexpr uint32_t TW = 1u << Shape::kLogW, TH = 1u << Shape::kLogH;
-    const uint32_t rows = P.band_end - P.band_begin;
-    const uint32_t tiles_x = (P.cam.width + TW - 1u) >> Shape::kLogW, tiles_y = (rows + TH - 1u) >> Shape::kLogH;
-    const uint32_t ntiles = tiles_x * tiles_y;
-    tile = 0xFFFFFFFFu;
-    // Workgroup b is observed to run on XCD b % 8.  tile_map picks how tiles are dealt to XCDs:
-    //   1  tile id = workgroup id (consecutive tiles on different XCDs)
-    //   2  tile ROWS dealt round-robin to XCDs (row r -> XCD r % 8) -- the default: the load
-    //      balance of 1 with each XCD's L2 still seeing whole rows of coherent rays
-    //   3  contiguous image bands per XCD (best L2 locality, but a sky band idles its XCD:
-    //      measured 1.77x slower on the headline scene)
-    // `order` (map 2 only): the same row -> XCD dealing, but each XCD starts its most expensive tiles first.
-    uint32_t t;
-    if (order) {
-        t = order[wg];
-    } else if (P.tile_map == 1u) {
-        t = wg;
-    } else if (P.tile_map == 2u) {
-        const uint32_t xcd = wg % kNumXcd, i = wg / kNumXcd;
-        const uint32_t rows_per_xcd = (tiles_y + kNumXcd - 1u) / kNumXcd;
-        const uint32_t ty = (i / tiles_x) * kNumXcd + xcd;
-        if (i >= rows_per_xcd * tiles_x || ty >= tiles_y) return false;
-        t = ty * tiles_x + (i % tiles_x);
-    } else {  // 3 (and anything else): contiguous bands
-        const uint32_t per_xcd = (ntiles + kNumXcd - 1u) / kNumXcd;
-        t = (wg % kNumXcd) * per_xcd + wg / kNumXcd;
-    }
-    if (t >= ntiles) return false;
-    tile = t;
-    const uint32_t pixel = threadIdx.x >> Shape::kLogS;  // the S sample lanes of a pixel are neighbours
-    gx = (t % tiles_x) * TW + (pixel & (TW - 1u));
-    gy = P.band_begin + (t / tiles_x) * TH + (pixel >> Shape::kLogW);
+    constexpr TileDims shape = tile_shape<S>();
+    const uint32_t rows = P.band_end - P.band_begin;  // (before the width is read: the compiler orders the factors of tiles_x * tiles_y by it, profiles/README.md)
+    const TileGrid grid = tile_grid(P.cam.width, rows, shape);
+    if (!workgroup_tile(wg, grid, P.tile_map, order, tile)) return false;
+    tile_lane_pixel(tile, threadIdx.x, grid.tiles_x, P.band_begin, shape, gx, gy);
     return gx < P.cam.width && gy < P.band_end;
 }
 __device__ __forceinline__ bool tile_pixel(const FrameParams &P, uint32_t &gx, uint32_t &gy) {
@@ -83,12 +42,8 @@ __device__ __forceinline__ bool tile_pixel(const FrameParams &P, uint32_t &gx, u
 // alive across the marches (lanes outside the image get coordinates outside it, as tile_pixel gives them).
 template <uint32_t S>
 __device__ __forceinline__ void lane_pixel(const FrameParams &P, uint32_t tile, uint32_t &gx, uint32_t &gy) {
-    using Shape = TileShape<S>;
-    constexpr uint32_t TW = 1u << Shape::kLogW, TH = 1u << Shape::kLogH;
-    const uint32_t tiles_x = (P.cam.width + TW - 1u) >> Shape::kLogW;
-    const uint32_t pixel = lane_now() >> Shape::kLogS;
-    gx = (tile % tiles_x) * TW + (pixel & (TW - 1u));
-    gy = P.band_begin + (tile / tiles_x) * TH + (pixel >> Shape::kLogW);
+    constexpr TileDims shape = tile_shape<S>();
+    tile_lane_pixel(tile, lane_now(), tiles_across(P.cam.width, shape), P.band_begin, shape, gx, gy);
 }
 
 // ---- longest-first dispatch ------------------------------------------------------------------------

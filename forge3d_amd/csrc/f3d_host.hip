@@ -30,6 +30,7 @@
 #include "f3d_retable.h"
 #include "f3d_setup.h"
 #include "f3d_tables.h"
+#include "f3d_tiles.h"
 
 using namespace f3d;
 
@@ -558,7 +559,7 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
             // one region of 64 slots per (frame in flight, tile, round of the tile's wave): f3d_scene.h WfQueues
             P.band_begin = s.row_begin;
             P.band_end = s.row_end;
-            const uint32_t lanes = P.sample_lanes ? P.sample_lanes : 1u;
+            const uint32_t lanes = sample_lanes_of(P);
             P.wf.regions_per_frame = frame_tile_count(P, nullptr) * ((P.spp + lanes - 1u) / lanes);
             const size_t regions = (size_t)s.fd_frames * P.wf.regions_per_frame, cap = regions * kWfRegion;
             P.wf.sun_o = (float4 *)s.mem.alloc(cap * sizeof(float4), "wavefront sun-ray queue");
@@ -649,6 +650,41 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
     clock.lap(kSetupPasses);
 }
 
+// The frame / trace kernels of frame `frame` (launch(), on `stream`) under the longest-first dispatch and the session's
+// timing: the waves leave their durations in tile_cost; the order is rebuilt from the newest durations every kOrderEvery
+// frames (a tile costs about the same from frame to frame), and the first frame of a session runs in image order.  The
+// timed bracket is what launch() enqueues alone -- in enqueue_band the frame kernel without its head (bench.py prices it
+// with ITS bytes: the head record it reads, not the head kernel's own traffic), so that it can be compared with
+// rocprofv3's per-kernel average.
+template <class Launch>
+void ordered_timed_launch(f3d_session &s, hipStream_t stream, uint32_t frame, Launch &&launch) {
+    constexpr int64_t kOrderEvery = 4;
+    FrameParams &P = s.params;
+    P.tile_cost = s.tile_cost;
+    P.tile_order = nullptr;
+    if (s.tile_cost && s.cost_frame >= 0) {
+        if (s.order_frame < 0 || s.cost_frame - s.order_frame >= kOrderEvery) {
+            hip_check(launch_tile_order(P, s.tile_cost, s.tile_order, stream), "tile order kernel");
+            s.order_frame = s.cost_frame;
+        }
+        P.tile_order = s.tile_order;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (s.timing) {
+        hip_check(hipEventCreate(&e0), "event");
+        hip_check(hipEventCreate(&e1), "event");
+        hip_check(hipEventRecord(e0, stream), "event record");
+    }
+    launch();
+    if (s.tile_cost) s.cost_frame = (int64_t)frame;
+    P.tile_order = nullptr;
+    P.tile_cost = nullptr;
+    if (s.timing) {
+        hip_check(hipEventRecord(e1, stream), "event record");
+        s.events.emplace_back(e0, e1);
+    }
+}
+
 // One band of one frame: frame head (sample-lane form) + frame kernel over the band's rows, on the band's
 // stream, after the frame before of this band and of its two neighbours (the head's spatial reuse reads the
 // previous frame's reservoirs of +-3 rows; everything else a band touches is its own).
@@ -679,34 +715,7 @@ void enqueue_band(f3d_session &s, f3d_session::Band &b, size_t index, uint32_t f
         }
     }
     if (P.sample_lanes > 1u) hip_check(launch_head(P, b.stream), "frame head kernel");
-    // longest-first dispatch: the order is rebuilt from the newest wave durations every kOrderEvery frames
-    // (a tile costs about the same from frame to frame); the first frame of a session runs in image order
-    constexpr int64_t kOrderEvery = 4;
-    P.tile_cost = s.tile_cost;
-    P.tile_order = nullptr;
-    if (s.tile_cost && s.cost_frame >= 0) {
-        if (s.order_frame < 0 || s.cost_frame - s.order_frame >= kOrderEvery) {
-            hip_check(launch_tile_order(P, s.tile_cost, s.tile_order, b.stream), "tile order kernel");
-            s.order_frame = s.cost_frame;
-        }
-        P.tile_order = s.tile_order;
-    }
-    // the timed bracket is the frame kernel alone (bench.py prices it with ITS bytes: the head record it reads,
-    // not the head kernel's own traffic), so that it can be compared with rocprofv3's per-kernel average
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (s.timing) {
-        hip_check(hipEventCreate(&e0), "event");
-        hip_check(hipEventCreate(&e1), "event");
-        hip_check(hipEventRecord(e0, b.stream), "event record");
-    }
-    hip_check(launch_frame(P, s.variant, b.stream), "frame kernel");
-    if (s.tile_cost) s.cost_frame = (int64_t)frame;
-    P.tile_order = nullptr;
-    P.tile_cost = nullptr;
-    if (s.timing) {
-        hip_check(hipEventRecord(e1, b.stream), "event record");
-        s.events.emplace_back(e0, e1);
-    }
+    ordered_timed_launch(s, b.stream, frame, [&] { hip_check(launch_frame(P, s.variant, b.stream), "frame kernel"); });
     if (piped) {
         hip_check(hipEventRecord(b.done[frame & 1u], b.stream), "band done");
         b.unjoined = true;
@@ -765,31 +774,10 @@ void enqueue_trace(f3d_session &s, uint32_t first, uint32_t count) {
     P.trace_first = first;
     P.band_begin = s.row_begin;
     P.band_end = s.row_end;
-    constexpr int64_t kOrderEvery = 4;
-    P.tile_cost = s.tile_cost;
-    P.tile_order = nullptr;
-    if (s.tile_cost && s.cost_frame >= 0) {
-        if (s.order_frame < 0 || s.cost_frame - s.order_frame >= kOrderEvery) {
-            hip_check(launch_tile_order(P, s.tile_cost, s.tile_order, s.stream), "tile order kernel");
-            s.order_frame = s.cost_frame;
-        }
-        P.tile_order = s.tile_order;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (s.timing) {
-        hip_check(hipEventCreate(&e0), "event");
-        hip_check(hipEventCreate(&e1), "event");
-        hip_check(hipEventRecord(e0, s.stream), "event record");
-    }
-    if (s.wavefront) hip_check(launch_trace_wavefront(P, count, s.wf_quorum, s.stream), "wavefront trace kernels");
-    else hip_check(launch_trace(P, count, s.stream), "trace kernel");
-    if (s.tile_cost) s.cost_frame = (int64_t)first;
-    P.tile_order = nullptr;
-    P.tile_cost = nullptr;
-    if (s.timing) {
-        hip_check(hipEventRecord(e1, s.stream), "event record");
-        s.events.emplace_back(e0, e1);
-    }
+    ordered_timed_launch(s, s.stream, first, [&] {
+        if (s.wavefront) hip_check(launch_trace_wavefront(P, count, s.wf_quorum, s.stream), "wavefront trace kernels");
+        else hip_check(launch_trace(P, count, s.stream), "trace kernel");
+    });
     s.trace_first = first;
     s.trace_count = count;
 }
@@ -1205,15 +1193,7 @@ int f3d_session_row_costs(f3d_session *s, float *out, uint32_t rows, char *err, 
         const uint32_t tiles = frame_tile_count(P, nullptr);
         std::vector<uint32_t> cost(tiles);
         hip_check(hipMemcpy(cost.data(), s->tile_cost, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost), "tile costs");
-        const uint32_t lanes = P.sample_lanes ? P.sample_lanes : 1u;
-        const uint32_t log_s = lanes == 1u ? 0u : (lanes == 2u ? 1u : (lanes == 4u ? 2u : 3u)), log_w = lanes <= 2u ? 3u : 2u, log_h = 6u - log_s - log_w;  // TileShape<S>
-        const uint32_t tiles_x = (s->width + (1u << log_w) - 1u) >> log_w, th = 1u << log_h;
-        std::vector<double> sum(rows, 0.0);
-        for (uint32_t t = 0; t < tiles; t++) {
-            const uint32_t r0 = (t / tiles_x) * th, r1 = std::min(rows, r0 + th);
-            for (uint32_t r = r0; r < r1; r++) sum[r] += (double)cost[t] / (double)(r1 - r0);
-        }
-        for (uint32_t r = 0; r < rows; r++) out[r] = (float)sum[r];
+        spread_tile_costs(cost.data(), s->width, rows, tile_shape(sample_lanes_of(P)), out);
         return F3D_STATUS_OK;
     } catch (const Failure &f) {
         return report(f, err, errlen);

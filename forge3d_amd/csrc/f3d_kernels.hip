@@ -1,5 +1,7 @@
 // forge3d_amd/csrc/f3d_kernels.hip -- gfx950 kernels of the terrain path tracer.
 // Host-callable launchers; the kernels themselves are in f3d_frame.h.
+#include <type_traits>
+
 #include "f3d_frame.h"
 
 namespace f3d {
@@ -19,19 +21,31 @@ hipError_t launch_horizon_build(const TerrainDev &terrain, float *table, hipStre
     hipLaunchKernelGGL(k_horizon_build, dim3(((B.bx + 7u) >> 3) * ((B.bz + 7u) >> 3)), dim3(kWave), 0, stream, B);
     return hipGetLastError();
 }
-static inline uint32_t frame_grid(const FrameParams &p, uint32_t lanes = 1u) {
-    const uint32_t log_s = lanes == 1u ? 0u : (lanes == 2u ? 1u : (lanes == 4u ? 2u : 3u));
-#if defined(F3D_TILE_LOGW_S4)
-    const uint32_t log_w = lanes <= 2u ? 3u : (lanes == 4u ? F3D_TILE_LOGW_S4 : 2u), log_h = 6u - log_s - log_w;
-#else
-    const uint32_t log_w = lanes <= 2u ? 3u : 2u, log_h = 6u - log_s - log_w;  // TileShape<S>
-#endif
-    const uint32_t rows = p.band_end - p.band_begin;
-    const uint32_t tiles_x = (p.cam.width + (1u << log_w) - 1u) >> log_w, tiles_y = (rows + (1u << log_h) - 1u) >> log_h;
-    if (tiles_y == 0u) return 0u;
-    if (p.tile_map == 2u) return ((tiles_y + kNumXcd - 1u) / kNumXcd) * tiles_x * kNumXcd;
-    return ((tiles_x * tiles_y + kNumXcd - 1u) / kNumXcd) * kNumXcd;
+// Workgroups of a launch over the band of p, one wave of `lanes` sample lanes a tile (f3d_tiles.h); the kernels that give
+// every lane a pixel of its own (k_head, k_merge, k_gbuffer, ...) tile 8 x 8 whatever p.sample_lanes says: lanes = 1.
+static inline TileGrid band_tiles(const FrameParams &p, uint32_t lanes) {
+    return tile_grid(p.cam.width, p.band_end - p.band_begin, tile_shape(lanes));
 }
+static inline uint32_t frame_grid(const FrameParams &p, uint32_t lanes = 1u) { return launch_size(band_tiles(p, lanes), p.tile_map); }
+
+// The instantiation table: a session's run-time sample-lane count and mesh flag as compile-time constants of a generic
+// lambda, which names its kernel family once.  with_lanes: false = no kernel has that many sample lanes.
+template <class F>
+static bool with_lanes(uint32_t lanes, F &&launch) {
+    switch (lanes) {
+        case 1: launch(std::integral_constant<uint32_t, 1u>{}); return true;
+        case 2: launch(std::integral_constant<uint32_t, 2u>{}); return true;
+        case 4: launch(std::integral_constant<uint32_t, 4u>{}); return true;
+        case 8: launch(std::integral_constant<uint32_t, 8u>{}); return true;
+        default: return false;
+    }
+}
+template <class F>
+static void with_mesh(bool mesh, F &&launch) {
+    if (mesh) launch(std::true_type{});
+    else launch(std::false_type{});
+}
+static inline bool has_mesh(const FrameParams &p) { return p.mesh.traversal_mode == 0u; }
 
 hipError_t launch_head(const FrameParams &p, hipStream_t stream) {  // the band's pixels, one lane each (8x8 tiles)
     if (frame_grid(p) == 0u) return hipSuccess;
@@ -49,96 +63,40 @@ hipError_t launch_head(const FrameParams &p, hipStream_t stream) {  // the band'
 #endif
 constexpr int kDrapeWaves = F3D_DRAPE_WAVES;
 hipError_t launch_frame(const FrameParams &p, int variant, hipStream_t stream) {
-    const uint32_t lanes = p.sample_lanes ? p.sample_lanes : 1u;
+    const uint32_t lanes = sample_lanes_of(p);
     if (frame_grid(p, lanes) == 0u) return hipSuccess;  // an empty band
     const dim3 grid(frame_grid(p, lanes)), block(kWave);
     // (F3D_FORCE_MESH_KERNEL=1: A/B switch, the mesh-capable instantiation for a terrain-only scene -- same results)
     static const bool force_mesh = getenv("F3D_FORCE_MESH_KERNEL") != nullptr;
-    const bool mesh = p.mesh.traversal_mode == 0u || force_mesh;
+    const bool mesh = has_mesh(p) || force_mesh;
+    const int budget = variant % 1000;  // 0: 80 VGPRs, 6 waves/SIMD; 104, 105: register-budget A/B variants
+    bool known = false;
     if (p.drape) {  // a draped session: the default variant of each sample-lane count (the host refuses the A/B variants)
-        if (variant % 1000 != 0) return hipErrorInvalidValue;
-        switch (lanes) {
-            case 1:
-                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 1, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 1, false>), grid, block, 0, stream, p);
-                break;
-            case 2:
-                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 2, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 2, false>), grid, block, 0, stream, p);
-                break;
-            case 4:
-                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 4, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 4, false>), grid, block, 0, stream, p);
-                break;
-            case 8:
-                if (mesh) hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 8, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, 8, false>), grid, block, 0, stream, p);
-                break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        known = budget == 0 && with_lanes(lanes, [&](auto S) {
+            with_mesh(mesh, [&](auto M) { hipLaunchKernelGGL((k_frame_drape<kDrapeWaves, S(), M()>), grid, block, 0, stream, p); });
+        });
+    } else if (budget == 0) {  // one wave per workgroup
+        known = with_lanes(lanes, [&](auto S) {
+            with_mesh(mesh, [&](auto M) { hipLaunchKernelGGL((k_frame<0, 6, S(), M()>), grid, block, 0, stream, p); });
+        });
+    } else if (budget == 104 && lanes == 1u) {
+        known = true;
+        with_mesh(mesh, [&](auto M) { hipLaunchKernelGGL((k_frame<0, 4, 1u, M()>), grid, block, 0, stream, p); });
+    } else if (budget == 105 && lanes == 4u) {
+        known = true;
+        with_mesh(mesh, [&](auto M) { hipLaunchKernelGGL((k_frame<0, 5, 4u, M()>), grid, block, 0, stream, p); });
     }
-    if (lanes != 1u) {  // one wave per workgroup (register-budget A/B variants for 4 and 8 lanes only)
-        switch (lanes * 1000 + (uint32_t)(variant % 1000)) {
-            case 2000:
-                if (mesh) hipLaunchKernelGGL((k_frame<0, 6, 2, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame<0, 6, 2>), grid, block, 0, stream, p);
-                break;
-            case 4000:
-                if (mesh) hipLaunchKernelGGL((k_frame<0, 6, 4, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame<0, 6, 4>), grid, block, 0, stream, p);
-                break;
-            case 4105:
-                if (mesh) hipLaunchKernelGGL((k_frame<0, 5, 4, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame<0, 5, 4>), grid, block, 0, stream, p);
-                break;
-            case 8000:
-                if (mesh) hipLaunchKernelGGL((k_frame<0, 6, 8, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((k_frame<0, 6, 8>), grid, block, 0, stream, p);
-                break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (variant % 1000) {
-        case 0:
-            if (mesh) hipLaunchKernelGGL((k_frame<0, 6, 1u, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_frame<0, 6>), grid, block, 0, stream, p);
-            break;  // default: 80 VGPRs, 6 waves/SIMD
-        case 104:
-            if (mesh) hipLaunchKernelGGL((k_frame<0, 4, 1u, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_frame<0, 4>), grid, block, 0, stream, p);
-            break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 // frames [p.frame_index, p.frame_index + frames) of the strip into p.trace (grid.y = frame)
 hipError_t launch_trace(const FrameParams &p, uint32_t frames, hipStream_t stream) {
-    const uint32_t lanes = p.sample_lanes ? p.sample_lanes : 1u;
+    const uint32_t lanes = sample_lanes_of(p);
     if (frame_grid(p, lanes) == 0u || frames == 0u) return hipSuccess;
     const dim3 grid(frame_grid(p, lanes), frames), block(kWave);
-    const bool mesh = p.mesh.traversal_mode == 0u;
-    switch (lanes) {
-        case 1:
-            if (mesh) hipLaunchKernelGGL((k_trace<6, 1, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_trace<6, 1>), grid, block, 0, stream, p);
-            break;
-        case 2:
-            if (mesh) hipLaunchKernelGGL((k_trace<6, 2, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_trace<6, 2>), grid, block, 0, stream, p);
-            break;
-        case 4:
-            if (mesh) hipLaunchKernelGGL((k_trace<6, 4, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_trace<6, 4>), grid, block, 0, stream, p);
-            break;
-        case 8:
-            if (mesh) hipLaunchKernelGGL((k_trace<6, 8, true>), grid, block, 0, stream, p);
-            else hipLaunchKernelGGL((k_trace<6, 8>), grid, block, 0, stream, p);
-            break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = with_lanes(lanes, [&](auto S) {
+        with_mesh(has_mesh(p), [&](auto M) { hipLaunchKernelGGL((k_trace<6, S(), M()>), grid, block, 0, stream, p); });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 // the wavefront form of launch_trace: primaries + queues, then the three queues through persistent waves
 template <class K>
@@ -150,18 +108,13 @@ static uint32_t persistent_grid(K kernel) {
     return (uint32_t)cus * (uint32_t)per_cu;
 }
 hipError_t launch_trace_wavefront(const FrameParams &p, uint32_t frames, uint32_t quorum, hipStream_t stream) {
-    const uint32_t lanes = p.sample_lanes ? p.sample_lanes : 1u;
+    const uint32_t lanes = sample_lanes_of(p);
     if (frame_grid(p, lanes) == 0u || frames == 0u) return hipSuccess;
     hipError_t err = hipMemsetAsync(p.wf.cursors, 0, 4u * sizeof(uint32_t), stream);
     if (err != hipSuccess) return err;
     const dim3 grid(frame_grid(p, lanes), frames), block(kWave);
-    switch (lanes) {
-        case 1: hipLaunchKernelGGL((k_wf_primary<6, 1>), grid, block, 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((k_wf_primary<6, 2>), grid, block, 0, stream, p); break;
-        case 4: hipLaunchKernelGGL((k_wf_primary<6, 4>), grid, block, 0, stream, p); break;
-        case 8: hipLaunchKernelGGL((k_wf_primary<6, 8>), grid, block, 0, stream, p); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (!with_lanes(lanes, [&](auto S) { hipLaunchKernelGGL((k_wf_primary<6, S()>), grid, block, 0, stream, p); }))
+        return hipErrorInvalidValue;
     static const uint32_t sun_grid = persistent_grid(k_wf_occl<true, 7>), ibl_grid = persistent_grid(k_wf_occl<false, 8>);
     WfOcclParams W{};
     W.terrain = p.terrain;
@@ -198,21 +151,15 @@ hipError_t launch_merge(const FrameParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 hipError_t launch_tile_order(const FrameParams &p, const uint32_t *cost, uint32_t *order, hipStream_t stream) {
-    const uint32_t lanes = p.sample_lanes ? p.sample_lanes : 1u;
-    const uint32_t log_s = lanes == 1u ? 0u : (lanes == 2u ? 1u : (lanes == 4u ? 2u : 3u));
-    const uint32_t log_w = lanes <= 2u ? 3u : 2u, log_h = 6u - log_s - log_w;  // TileShape<S>
-    const uint32_t rows = p.band_end - p.band_begin;
-    TileOrderParams B{cost, order, (p.cam.width + (1u << log_w) - 1u) >> log_w, (rows + (1u << log_h) - 1u) >> log_h};
+    const TileGrid tiles = band_tiles(p, sample_lanes_of(p));
+    TileOrderParams B{cost, order, tiles.tiles_x, tiles.tiles_y};
     hipLaunchKernelGGL(k_tile_order, dim3(kNumXcd), dim3(1024), 0, stream, B);
     return hipGetLastError();
 }
 uint32_t frame_tile_count(const FrameParams &p, uint32_t *grid) {
-    const uint32_t lanes = p.sample_lanes ? p.sample_lanes : 1u;
-    const uint32_t log_s = lanes == 1u ? 0u : (lanes == 2u ? 1u : (lanes == 4u ? 2u : 3u));
-    const uint32_t log_w = lanes <= 2u ? 3u : 2u, log_h = 6u - log_s - log_w;
-    const uint32_t rows = p.band_end - p.band_begin;
+    const uint32_t lanes = sample_lanes_of(p);
     if (grid) *grid = frame_grid(p, lanes);
-    return ((p.cam.width + (1u << log_w) - 1u) >> log_w) * ((rows + (1u << log_h) - 1u) >> log_h);
+    return band_tiles(p, lanes).count();
 }
 hipError_t launch_gbuffer(const FrameParams &p, float4 *gbuffer_n, float *depth, hipStream_t stream) {
     hipLaunchKernelGGL(k_gbuffer, dim3(frame_grid(p)), dim3(kWave), 0, stream, p, gbuffer_n, depth);
@@ -245,16 +192,14 @@ hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream) {
 hipError_t launch_query(const QueryParams &p, hipStream_t stream) {
     if (p.count == 0u) return hipSuccess;
     const dim3 grid((p.count + kWave - 1u) / kWave), block(kWave);
-    if (p.frame.mesh.traversal_mode == 0u) hipLaunchKernelGGL((k_query<true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((k_query<false>), grid, block, 0, stream, p);
+    with_mesh(has_mesh(p.frame), [&](auto M) { hipLaunchKernelGGL((k_query<M()>), grid, block, 0, stream, p); });
     return hipGetLastError();
 }
 hipError_t launch_raster(const RasterParams &p, hipStream_t stream) {
     const uint32_t total = p.rows * p.cols;
     if (total == 0u || p.target_count == 0u) return hipSuccess;
     const dim3 grid((total + kWave - 1u) / kWave), block(kWave);
-    if (p.frame.mesh.traversal_mode == 0u) hipLaunchKernelGGL((k_raster<true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((k_raster<false>), grid, block, 0, stream, p);
+    with_mesh(has_mesh(p.frame), [&](auto M) { hipLaunchKernelGGL((k_raster<M()>), grid, block, 0, stream, p); });
     return hipGetLastError();
 }
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream) {

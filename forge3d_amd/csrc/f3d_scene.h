@@ -228,7 +228,7 @@ struct FrameParams {
     const float4 *gbuffer_n;        // xyz = centre-ray normal ((0,0,1) on sky), w = hit code
     uint32_t *stats;                // [0] max m2 bits, [1] nonfinite, [2] any_valid, [3] bad
     uint32_t collect_stats;         // this frame closes a convergence window
-    uint32_t tile_map;              // workgroup -> tile mapping (f3d_kernels.hip tile_pixel)
+    uint32_t tile_map;              // workgroup -> tile mapping (f3d_tiles.h workgroup_tile)
     uint32_t sample_lanes;          // lanes per pixel in the frame kernel: 1 (frame_pixel), 2, 4, 8 (frame_lanes)
     uint2 *head;                    // sample-lane form only: per-pixel record of k_head {reuse_w bits, flags}
     float2 *sun_clear;              // per pixel {parameter after which no sun ray of the pixel meets terrain, depth of the centre hit}; null = off
@@ -251,6 +251,7 @@ struct FrameParams {
     WfQueues wf;          // wavefront form of the trace batch (sun_o == null: k_trace traces the rays itself)
     const DrapeDev *drape;  // per-texel terrain albedo (null: none); read by the draped kernels only
 };
+F3D_HD uint32_t sample_lanes_of(const FrameParams &p) { return p.sample_lanes ? p.sample_lanes : 1u; }  // (0: unset, one lane)
 
 // Re-arm / re-aim of a live session (f3d_session_rearm, f3d_session_reaim; k_rearm, k_reaim): frame = the new uniforms
 // over the whole strip
