@@ -175,6 +175,21 @@ RASTER_TOWARD_POINT, RASTER_ALONG_DIRECTION = 0, 1
 RASTER_TERRAIN_ONLY, RASTER_CURVED, RASTER_DEVICE_POINTERS, RASTER_NO_WAIT, RASTER_SESSION_SUN = 1, 2, 4, 8, 16
 
 
+class HorizonDesc(C.Structure):
+    """f3d_session_horizon_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("lift", C.c_float), ("azimuth_count", C.c_uint32),
+        ("azimuths", C.c_void_p), ("horizon", C.c_void_p), ("sky_view", C.c_void_p),
+        ("reserved", C.c_uint32),
+    ]
+
+
+HORIZON_CURVED, HORIZON_DEVICE_POINTERS, HORIZON_NO_WAIT = 2, 4, 8
+HORIZON_MAX_AZIMUTHS = 256  # F3D_HORIZON_MAX_AZIMUTHS
+
+
 class DrapeDesc(C.Structure):
     """f3d_session_drape_desc"""
     _fields_ = [
@@ -233,6 +248,7 @@ ABI = [
     ("f3d_session_reterrain", C.c_int, [C.c_void_p, _P(ReterrainDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_query", C.c_int, [C.c_void_p, _P(QueryDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_raster", C.c_int, [C.c_void_p, _P(RasterDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_horizon", C.c_int, [C.c_void_p, _P(HorizonDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape", C.c_int, [C.c_void_p, _P(DrapeDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),

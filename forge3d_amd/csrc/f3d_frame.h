@@ -14,6 +14,7 @@
 #include "f3d_shade.h"
 #include "f3d_query.h"
 #include "f3d_raster.h"
+#include "f3d_horizon.h"
 #include "f3d_lds.h"
 #include "f3d_tiles.h"
 
@@ -826,6 +827,49 @@ __global__ __launch_bounds__(kWave) void k_raster(const RasterParams R) {
         seen += visible ? 1u : 0u;
     }
     if (R.count && have) R.count[n] = seen;
+}
+
+// Horizon rasters on a live session (f3d_session_horizon; f3d_horizon.h): one wave a workgroup, one lane a DEM sample of the
+// region -- 64 consecutive samples (the planes are written 256 contiguous bytes a wave), or with R.block an 8 x 8 block of the
+// region (the 64 lines of an azimuth stay together at the coarse levels; measured: profiles/README.md).  The lane keeps its
+// sample's origin and its sky-view sum in registers across the azimuths; the walk has no wave primitive in it, and all it
+// needs of LDS is the per-level layout of the band table (128 bytes).
+struct HorizonLevels {
+    const uint32_t *table;  // {band_offset, band_shift} per level
+    __device__ __forceinline__ void band_entry(const TerrainDev &, uint32_t level, uint32_t &offset, uint32_t &shift) const {
+        const uint2 e = *reinterpret_cast<const uint2 *>(table + 2u * level);
+        offset = e.x;
+        shift = e.y;
+    }
+};
+__global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
+    __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
+    if (threadIdx.x < kMaxLevels) {
+        table[2u * threadIdx.x] = R.terrain.band_offset[threadIdx.x];
+        table[2u * threadIdx.x + 1u] = R.terrain.band_shift[threadIdx.x];
+    }
+    __syncthreads();
+    const HorizonLevels levels{table};
+    const uint32_t total = R.rows * R.cols;
+    uint32_t n = blockIdx.x * kWave + threadIdx.x;
+    bool have = n < total;
+    if (R.block != 0u) {
+        const uint32_t tiles_x = (R.cols + 7u) >> 3;
+        const uint32_t r = (blockIdx.x / tiles_x) * 8u + (threadIdx.x >> 3), c = (blockIdx.x % tiles_x) * 8u + (threadIdx.x & 7u);
+        have = r < R.rows && c < R.cols;
+        n = r * R.cols + c;
+    }
+    if (!have) return;  // (no wave primitive below)
+    uint32_t i, j;
+    const V3 o = horizon_origin(R, n, i, j);
+    float sum = 0.0f;
+    for (uint32_t k = 0u; k < R.azimuth_count; k++) {
+        const float2 az = R.azimuths[k];
+        const float H = horizon_walk(R.terrain, o, i, j, az.x, az.y, horizon_curvature(R, az.x, az.y), R.step_cap, levels);
+        if (R.horizon) R.horizon[(size_t)k * total + n] = H;
+        sum = sum + horizon_sky_term(H, az.x, az.y);
+    }
+    if (R.sky_view) R.sky_view[n] = 1.0f - sum / (float)R.azimuth_count;
 }
 
 // ---- acceleration-table builders (reference build_minmax_mips,

@@ -297,4 +297,19 @@ struct RasterParams {
     uint32_t *count;             // rows * cols: targets whose bit is 1
 };
 
+// Horizon rasters on a live session (f3d_session_horizon; k_horizon, f3d_horizon.h): terrain only, one lane a DEM sample of
+// the region, a loop over the azimuths.  Either output may be null.
+struct HorizonParams {
+    TerrainDev terrain;
+    uint32_t curved;             // the curvature policy of the raster's sun rays
+    uint32_t row0, col0, rows, cols;  // the region, as a raster's
+    float lift;                  // added to the sample's height, >= 0
+    uint32_t azimuth_count;      // 1 .. kHorizonMaxAzimuths
+    uint32_t step_cap;           // horizon_step_cap(terrain)
+    uint32_t block;              // a wave's footprint: 0 = 64 consecutive samples of the region, 1 = an 8 x 8 block of it
+    const float2 *azimuths;      // (dx, dz) each
+    float *horizon;              // azimuth_count x rows * cols
+    float *sky_view;             // rows * cols
+};
+
 }  // namespace f3d

@@ -600,6 +600,84 @@ class TerrainSession:
         return self.visibility(d, toward=False, curved=curved, terrain_only=terrain_only, lift=np.float32(self.SURFACE_BIAS),
                                region=region, masks=False, count=True)
 
+    # -- horizon rasters: horizon slopes, sky-view factor -----------------------------------
+    @staticmethod
+    def horizon_directions(azimuths=16):
+        """The float32 (K, 2) rows ``(dx, dz)`` a horizon() / sky_view_factor() call with these ``azimuths`` uses.  An int N:
+        the compass headings ``360 k / N`` degrees, k = 0 .. N - 1, in the convention of ``sun_azimuth_deg`` -- ``(dx, dz) =
+        (sin a, -cos a)``, computed in float64 and rounded to float32 (0 is north, -z; 90 east, +x).  A (K, 2) array is used as
+        given; a torch tensor stays a tensor.  ``(dx_k, s, dz_k)`` is then the direction whose visibility ``s > H_k`` answers."""
+        if isinstance(azimuths, (int, np.integer)) and not isinstance(azimuths, bool):
+            n = int(azimuths)
+            if not 1 <= n <= _native.HORIZON_MAX_AZIMUTHS:
+                raise ValueError(f"azimuths must be 1 to {_native.HORIZON_MAX_AZIMUTHS}, got {n}")
+            a = np.radians(360.0 * np.arange(n, dtype=np.float64) / n)
+            return np.stack([np.sin(a), -np.cos(a)], 1).astype(np.float32)
+        if type(azimuths).__module__.split(".")[0] == "torch":
+            import torch
+
+            d = azimuths.to(torch.float32)
+            if d.ndim != 2 or d.shape[1] != 2:
+                raise ValueError(f"expected shape (K, 2), got {tuple(azimuths.shape)}")
+            return d.contiguous()
+        d = np.ascontiguousarray(azimuths, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] != 2:
+            raise ValueError(f"expected shape (K, 2), got {d.shape}")
+        return d
+
+    def _horizon(self, azimuths, lift, curved, region, planes, sky_view, wait):
+        dem_h, dem_w = self.dem_shape
+        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
+        if min(row0, col0, rows, cols) < 0:
+            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        d = self.horizon_directions(azimuths)
+        k, n = int(d.shape[0]), rows * cols
+        q = _native.HorizonDesc()
+        q.struct_size = C.sizeof(_native.HorizonDesc)
+        q.flags = _native.HORIZON_CURVED if curved else 0
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.lift = float(lift)
+        q.azimuth_count = k
+        tensors = not isinstance(d, np.ndarray)
+        if tensors:
+            import torch
+
+            if not d.is_cuda:
+                raise ValueError("a tensor horizon needs a tensor on the session's device (NumPy arrays take the host form)")
+            q.flags |= _native.HORIZON_DEVICE_POINTERS | (0 if wait else _native.HORIZON_NO_WAIT)
+            h_out = torch.empty((k, rows, cols), dtype=torch.float32, device=d.device) if planes else None
+            s_out = torch.empty((rows, cols), dtype=torch.float32, device=d.device) if sky_view else None
+            q.azimuths = d.data_ptr() if k else None
+            q.horizon, q.sky_view = (h_out.data_ptr() if planes else None), (s_out.data_ptr() if sky_view else None)
+        else:
+            if not wait:
+                raise ValueError("wait=False is for tensor horizons: results in host memory are there when the call returns")
+            h_out = np.zeros((k, rows, cols), np.float32) if planes else None
+            s_out = np.zeros((rows, cols), np.float32) if sky_view else None
+            q.azimuths = d.ctypes.data if k else None
+            q.horizon, q.sky_view = (h_out.ctypes.data if planes else None), (s_out.ctypes.data if sky_view else None)
+        self._check(self._lib.f3d_session_horizon(self._handle, C.byref(q), self._err, len(self._err)))  # (d lives until here)
+        return h_out, s_out
+
+    def horizon(self, azimuths=16, *, lift: float = SURFACE_BIAS, curved: bool = False, region=None, sky_view: bool = False,
+                wait: bool = True):
+        """One f3d_session_horizon: for every DEM sample of ``region`` (``(row0, col0, rows, cols)``, default the whole DEM),
+        lifted by ``lift`` >= 0, and every azimuth, the slope ``H`` under which the ground hides the sky along that azimuth --
+        the supremum of ``(y - k t^2 - o.y) / t`` over the terrain ahead (terrain only: a mesh is not a horizon), -inf where no
+        terrain lies ahead.  ``azimuths``: see horizon_directions().  ``(dx, H, dz)`` is the grazing direction of visibility()
+        along a direction with the same ``curved``; for unit ``(dx, dz)`` H is the tangent of the horizon's elevation.  A
+        NumPy array or an int takes the host form (blocking); a torch tensor on the session's device the device form (results
+        are tensors; ``wait=False`` returns with the kernel in flight on the session's stream).
+        Returns the float32 array (K, rows, cols), and ``(horizon, sky_view)`` with ``sky_view=True``."""
+        h, s = self._horizon(azimuths, lift, curved, region, True, sky_view, wait)
+        return (h, s) if sky_view else h
+
+    def sky_view_factor(self, azimuths=16, *, lift: float = SURFACE_BIAS, curved: bool = False, region=None, wait: bool = True):
+        """The horizontal-surface sky-view factor (Dozier-Frew / Zaksek) of every DEM sample of ``region``: ``1 - mean_k
+        sin(elevation of horizon k)``, horizons below the horizontal counting 0.  float32 (rows, cols); the K horizon planes
+        are never materialised, on the device or here.  Arguments as horizon()."""
+        return self._horizon(azimuths, lift, curved, region, False, True, wait)[1]
+
     def certificates(self) -> dict:
         """Diagnostics (synchronises): content hashes of the sun-ray and primary-ray certificates."""
         out = (C.c_uint64 * 2)()

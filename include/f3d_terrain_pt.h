@@ -522,6 +522,51 @@ typedef struct f3d_session_raster_desc {
     uint32_t *count;       /* rows * cols, or NULL */
 } f3d_session_raster_desc;
 int f3d_session_raster(f3d_session *session, const f3d_session_raster_desc *desc, char *err, size_t errlen);
+/* ---- horizon rasters: horizon slopes and sky-view factor ----------------------------------------------------------------------
+ * For every DEM sample of a region and every azimuth, the slope under which the GROUND hides the sky (terrain only: a
+ * session with a mesh answers for its terrain) -- one max-slope walk of the min/max pyramid per sample per azimuth
+ * (k_horizon; the contract, the leaf's closed form and the bound are at the head of csrc/f3d_horizon.h).  The sample stands
+ * on the lifted lattice point o of the visibility rasters (lift >= 0); an azimuth is a horizontal direction (dx, dz), two
+ * f32 used as given; with p(t) = (o.x + t dx, o.z + t dz) and y the bilinear surface,
+ *     H = sup over t > 0, p(t) inside the footprint, of (y(p(t)) - k t^2 - o.y) / t
+ * k = (dx^2 + dz^2) inv_two_r_prime with CURVED on a scene with earth curvature, else 0: (dx, H, dz) is the grazing direction
+ * of the visibility rasters' rays under the same flag.  For a unit (dx, dz) H is the tangent of the horizon's elevation.
+ * No terrain along the azimuth (a border sample looking outward; a line along the DEM's last row or column, where the
+ * march finds no cell either): -inf.  lift == 0 includes the limit t -> 0+.  All arithmetic is f32, one rounding per operation.
+ *   horizon   azimuth_count x rows * cols f32: plane k is azimuth k, sample n = r * cols + c
+ *   sky_view  rows * cols f32: 1 - (sum_k s_k) / azimuth_count, s_k = max(h, 0) / sqrt(1 + h^2), h = H_k / sqrt(dx_k^2 + dz_k^2)
+ *             (the horizontal-surface sky-view factor; -inf and NaN azimuths contribute 0), summed in f32 for k = 0, 1, ...
+ * Either may be NULL, not both; with horizon NULL nothing of size azimuth_count x rows * cols is written or allocated.
+ * CURVED, DEVICE_POINTERS, NO_WAIT and the ordering on the session stream are the raster's; nothing a frame launch reads is
+ * written.
+ *   host pointers (default)  blocking; staged through the visibility rasters' scratch buffer (the outputs asked for + 8 bytes
+ *       an azimuth), grown only for a larger call than any before, against memory_budget_bytes (too small: status 2, session
+ *       unchanged).  A non-finite or zero (dx, dz): refused
+ *   DEVICE_POINTERS          azimuths (8-byte aligned), horizon and sky_view are device memory; nothing is copied or allocated.
+ *       A non-finite or zero (dx, dz): that plane is NaN
+ * A walk that exceeds its step cap (no DEM does) writes NaN for that azimuth of that sample.
+ * Refused (status 1, session unchanged): an unknown flag, NO_WAIT without DEVICE_POINTERS, a region that is empty or reaches
+ * outside the DEM, a non-finite or negative lift, azimuth_count 0 or above F3D_HORIZON_MAX_AZIMUTHS, NULL azimuths, both
+ * outputs NULL.  No ABI version bump: detected by the symbol f3d_session_horizon. */
+#define F3D_HORIZON_CURVED 2u
+#define F3D_HORIZON_DEVICE_POINTERS 4u
+#define F3D_HORIZON_NO_WAIT 8u
+#define F3D_HORIZON_MAX_AZIMUTHS 256u
+typedef struct f3d_session_horizon_desc {
+    uint32_t struct_size;   /* = sizeof(f3d_session_horizon_desc) of the caller's header */
+    uint32_t flags;         /* F3D_HORIZON_CURVED | _DEVICE_POINTERS | _NO_WAIT */
+    uint32_t row0;          /* the region, in DEM samples: rows [row0, row0 + rows), columns [col0, col0 + cols) */
+    uint32_t col0;
+    uint32_t rows;
+    uint32_t cols;
+    float lift;             /* added to every sample's height, >= 0 */
+    uint32_t azimuth_count; /* 1 .. F3D_HORIZON_MAX_AZIMUTHS */
+    const float *azimuths;  /* azimuth_count x 2 f32: (dx, dz) */
+    float *horizon;         /* azimuth_count x rows * cols, or NULL */
+    float *sky_view;        /* rows * cols, or NULL */
+    uint32_t reserved;      /* 0 */
+} f3d_session_horizon_desc;
+int f3d_session_horizon(f3d_session *session, const f3d_session_horizon_desc *desc, char *err, size_t errlen);
 /* ---- drape: an image laid over the terrain, per-texel albedo ---------------------------------------------------------------
  * What an image changes on top of a re-aim, still without a new session: the albedo of TERRAIN hits.  The drape is
  * image[rows][cols] of linear RGB reflectances, f32, row-major, `channels` (3 or 4; a fourth channel is ignored) values a
