@@ -190,6 +190,20 @@ HORIZON_CURVED, HORIZON_DEVICE_POINTERS, HORIZON_NO_WAIT = 2, 4, 8
 HORIZON_MAX_AZIMUTHS = 256  # F3D_HORIZON_MAX_AZIMUTHS
 
 
+class IrradiationDesc(C.Structure):
+    """f3d_session_irradiation_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("lift", C.c_float), ("direction_count", C.c_uint32),
+        ("directions", C.c_void_p), ("energy", C.c_void_p), ("count", C.c_void_p), ("normal", C.c_void_p),
+        ("reserved", C.c_uint32),
+    ]
+
+
+IRRADIATION_TERRAIN_ONLY, IRRADIATION_CURVED, IRRADIATION_DEVICE_POINTERS, IRRADIATION_NO_WAIT, IRRADIATION_HORIZONTAL = 1, 2, 4, 8, 16
+
+
 class DrapeDesc(C.Structure):
     """f3d_session_drape_desc"""
     _fields_ = [
@@ -249,6 +263,7 @@ ABI = [
     ("f3d_session_query", C.c_int, [C.c_void_p, _P(QueryDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_raster", C.c_int, [C.c_void_p, _P(RasterDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_horizon", C.c_int, [C.c_void_p, _P(HorizonDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_irradiation", C.c_int, [C.c_void_p, _P(IrradiationDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape", C.c_int, [C.c_void_p, _P(DrapeDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),

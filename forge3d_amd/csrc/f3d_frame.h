@@ -15,6 +15,7 @@
 #include "f3d_query.h"
 #include "f3d_raster.h"
 #include "f3d_horizon.h"
+#include "f3d_irradiation.h"
 #include "f3d_lds.h"
 #include "f3d_tiles.h"
 
@@ -870,6 +871,42 @@ __global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
         sum = sum + horizon_sky_term(H, az.x, az.y);
     }
     if (R.sky_view) R.sky_view[n] = 1.0f - sum / (float)R.azimuth_count;
+}
+
+// Irradiation rasters on a live session (f3d_session_irradiation; f3d_irradiation.h): k_raster's shape -- one wave a
+// workgroup, 64 consecutive samples of the region, the wave's LdsPending rows, a wave-uniform trip count over the directions,
+// which every lane reads at the same address.  A lane keeps its sample's origin, gradient, sum and count in registers across the
+// directions and writes each output it owns with one ordinary store; nothing is shared between waves.
+template <bool MESH>
+__global__ __launch_bounds__(kWave) void k_irradiation(const IrradiationParams R) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+    typename PendingFor<MESH>::type pend{make_pending(lds, R.frame.terrain)};
+    const uint32_t total = R.rows * R.cols, n = blockIdx.x * kWave + threadIdx.x;
+    const bool have = n < total;
+    uint32_t i = 0u, j = 0u;
+    const V3 o = have ? irradiation_origin(R, n, i, j) : V3{0.0f, 0.0f, 0.0f};
+    const IrradiationSlope s = have ? irradiation_slope(R, i, j) : IrradiationSlope{0.0f, 0.0f, 1.0f};
+    float sum = 0.0f;
+    uint32_t seen = 0u;
+    for (uint32_t k = 0u; k < R.direction_count; k++) {  // (wave-uniform: the lanes meet again after every direction)
+        const float4 dir = R.directions[k];
+        bool lit = false;
+        float term = 0.0f;
+        if (have) term = irradiation_term(R, o, s, dir, pend, lit);
+        if (lit) {
+            sum = sum + term;
+            seen += 1u;
+        }
+    }
+    if (!have) return;
+    if (R.energy) R.energy[n] = sum;
+    if (R.count) R.count[n] = seen;
+    if (R.normal) {
+        const V3 nrm = irradiation_normal(s);
+        R.normal[3u * (size_t)n] = nrm.x;
+        R.normal[3u * (size_t)n + 1u] = nrm.y;
+        R.normal[3u * (size_t)n + 2u] = nrm.z;
+    }
 }
 
 // ---- acceleration-table builders (reference build_minmax_mips,

@@ -312,4 +312,19 @@ struct HorizonParams {
     float *sky_view;             // rows * cols
 };
 
+// Irradiation rasters on a live session (f3d_session_irradiation; k_irradiation, f3d_irradiation.h): frame as for a raster,
+// one lane a DEM sample of the region, a loop over the directions.  Any output may be null, not all.
+struct IrradiationParams {
+    FrameParams frame;
+    uint32_t curved;             // the sun rays' curvature policy
+    uint32_t horizontal;         // the beam on a horizontal plane: the gradient is (0, 0) and is not loaded
+    uint32_t row0, col0, rows, cols;  // the region, as a raster's
+    float lift;                  // added to the sample's height
+    uint32_t direction_count;    // 0 only with normal alone
+    const float4 *directions;    // (x, y, z, weight) each: toward the sun
+    float *energy;               // rows * cols: the sum of weight * cosine over the unblocked terms
+    uint32_t *count;             // rows * cols: terms that contributed
+    float *normal;               // rows * cols x 3: the unit normal the cosine is taken against
+};
+
 }  // namespace f3d

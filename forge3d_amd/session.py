@@ -55,6 +55,7 @@ class TerrainSession:
             self._handle = C.c_void_p(None)
             _native.raise_status(rc, err.value.decode("utf-8", "replace"))
         self.width, self.height = int(width), int(height)
+        self._device = int(device)
         # what rearm() keeps when a value is not given: the descriptor's re-armable members as the library holds them
         self._armed = {"sun_azimuth_deg": float(desc.sun_azimuth_deg), "sun_elevation_deg": float(desc.sun_elevation_deg),
                        "sun_intensity": float(desc.sun_intensity), "sun_color": tuple(float(c) for c in desc.sun_color),
@@ -677,6 +678,142 @@ class TerrainSession:
         sin(elevation of horizon k)``, horizons below the horizontal counting 0.  float32 (rows, cols); the K horizon planes
         are never materialised, on the device or here.  Arguments as horizon()."""
         return self._horizon(azimuths, lift, curved, region, False, True, wait)[1]
+
+    # -- irradiation rasters: beam energy over a sun track, surface normals --------------------
+    @staticmethod
+    def irradiation_terms(directions, weights=None):
+        """The (K, 4) float32 rows ``(x, y, z, weight)`` an irradiation() call with these arguments sends: ``directions`` (K, 3)
+        with ``weights`` (K,), or (K, 4) with the weight in the last column (``weights`` must then be None); a direction with
+        ``y <= 0`` -- the sun below the horizontal -- gets weight 0.  A torch tensor stays a tensor."""
+        tensors = type(directions).__module__.split(".")[0] == "torch"
+        if tensors:
+            import torch
+
+            d = directions.to(torch.float32)
+        else:
+            d = np.asarray(directions, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] not in (3, 4):
+            raise ValueError(f"expected directions of shape (K, 3) or (K, 4), got {tuple(d.shape)}")
+        if d.shape[1] == 4:
+            if weights is not None:
+                raise ValueError("(K, 4) directions carry their weights: weights must be None")
+            xyz, w = d[:, :3], d[:, 3]
+        else:
+            if weights is None:
+                raise ValueError("(K, 3) directions need weights (K,)")
+            if tensors:
+                w = torch.as_tensor(weights, dtype=torch.float32, device=d.device).reshape(-1)
+            else:
+                w = np.asarray(weights, dtype=np.float32).reshape(-1)
+            if w.shape[0] != d.shape[0]:
+                raise ValueError(f"{d.shape[0]} directions but {w.shape[0]} weights")
+            xyz = d
+        if tensors:
+            w = torch.where(xyz[:, 1] > 0.0, w, torch.zeros_like(w))
+            return torch.cat([xyz, w[:, None]], 1).contiguous()
+        w = np.where(xyz[:, 1] > 0.0, w, np.float32(0.0)).astype(np.float32)
+        return np.ascontiguousarray(np.concatenate([xyz, w[:, None]], 1), dtype=np.float32)
+
+    def _irradiation(self, terms, flags, lift, region, energy, count, normal, wait, device=None):
+        dem_h, dem_w = self.dem_shape
+        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
+        if min(row0, col0, rows, cols) < 0:
+            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        q = _native.IrradiationDesc()
+        q.struct_size = C.sizeof(_native.IrradiationDesc)
+        q.flags = flags
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.lift = float(lift)
+        k = 0 if terms is None else int(terms.shape[0])
+        q.direction_count = k
+        tensors = device is not None or (terms is not None and not isinstance(terms, np.ndarray))
+        if tensors:
+            import torch
+
+            if terms is not None and not terms.is_cuda:
+                raise ValueError("a tensor irradiation needs a tensor on the session's device (NumPy arrays take the host form)")
+            q.flags |= _native.IRRADIATION_DEVICE_POINTERS | (0 if wait else _native.IRRADIATION_NO_WAIT)
+            make = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device if terms is None else terms.device)
+            e_out = make((rows, cols), torch.float32) if energy else None
+            c_out = make((rows, cols), torch.int32) if count else None
+            n_out = make((rows, cols, 3), torch.float32) if normal else None
+            q.directions = terms.data_ptr() if k else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+        else:
+            if not wait:
+                raise ValueError("wait=False is for tensor irradiations: results in host memory are there when the call returns")
+            e_out = np.zeros((rows, cols), np.float32) if energy else None
+            c_out = np.zeros((rows, cols), np.uint32) if count else None
+            n_out = np.zeros((rows, cols, 3), np.float32) if normal else None
+            q.directions = terms.ctypes.data if k else None
+            ptr = lambda a: None if a is None else a.ctypes.data
+        q.energy, q.count, q.normal = ptr(e_out), ptr(c_out), ptr(n_out)
+        self._check(self._lib.f3d_session_irradiation(self._handle, C.byref(q), self._err, len(self._err)))  # (terms lives until here)
+        return e_out, c_out, n_out
+
+    def irradiation(self, directions, weights=None, *, horizontal: bool = False, curved: bool = True, terrain_only: bool = False,
+                    lift: float = SURFACE_BIAS, region=None, count: bool = False, wait: bool = True):
+        """One f3d_session_irradiation: for every DEM sample of ``region`` (``(row0, col0, rows, cols)``, default the whole DEM)
+        the energy the direct beam delivers over the sun positions ``directions`` (toward the sun; (K, 3) with ``weights``
+        (K,), or (K, 4) with the weight in the last column; they need not be unit): the sum over the positions of ``weight x
+        cos(incidence on the local slope)`` wherever that cosine is positive and the shadow ray -- the one shadow_mask()
+        marches, from the sample lifted by ``lift``, under ``curved`` / ``terrain_only`` -- is unblocked.  Weights in W/m^2 x
+        hours give Wh/m^2.  A facet that faces away from a position marches no ray for it.  A direction with ``y <= 0`` (the
+        sun below the horizontal) gets weight 0 here, as sun_hours() drops it.  ``horizontal``: the beam on a horizontal plane
+        (the cosine is the sine of the sun's elevation) instead of the slope.  The slope is surface_normals()'s.  A NumPy
+        array takes the host form (blocking); a torch tensor on the session's device the device form (results are tensors;
+        ``wait=False`` returns with the kernel in flight on the session's stream).
+        Returns the float32 array (rows, cols), or ``(energy, count)`` with ``count=True``: the uint32 array (int32 bits as a
+        tensor) of the number of positions that contributed."""
+        terms = self.irradiation_terms(directions, weights)
+        flags = ((_native.IRRADIATION_HORIZONTAL if horizontal else 0) | (_native.IRRADIATION_CURVED if curved else 0)
+                 | (_native.IRRADIATION_TERRAIN_ONLY if terrain_only else 0))
+        e, c, _ = self._irradiation(terms, flags, lift, region, True, count, False, wait)
+        return (e, c) if count else e
+
+    def surface_normals(self, region=None, wait: bool = True):
+        """The unit surface normals irradiation() takes its cosines against, float32 (rows, cols, 3) as ``(x, y, z)`` with y up:
+        ``(-gx, 1, -gz) / sqrt(gx^2 + gz^2 + 1)`` where ``(gx, gz)`` is the central difference (one-sided on the DEM's border) of
+        the heights the session holds NOW -- exaggeration applied, reterrain() followed -- over the sample spacing.  Slope and
+        aspect follow from them: the slope angle is ``arccos(n_y)`` (its tangent ``hypot(n_x, n_z) / n_y``), and the aspect --
+        the compass heading the facet faces, downhill, in the convention of ``sun_azimuth_deg`` (0 north = -z, 90 east = +x) --
+        is ``atan2(n_x, -n_z)``, undefined where the slope is 0.  No ray is marched.  Returns a NumPy array (host form,
+        blocking); with ``wait=False`` a torch tensor on the session's device, the kernel in flight on the session's stream."""
+        device = None
+        if not wait:
+            import torch
+
+            device = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+        return self._irradiation(None, 0, 0.0, region, False, False, True, wait, device)[2]
+
+    def insolation(self, track, *, dni=None, dhi=None, azimuths=16, **irradiation_kwargs) -> dict:
+        """A solar-exposure map over a sun track (``insolation.sun_track``: ``directions``, ``elevation_deg``, ``hours``), in
+        Wh/m^2, float32 (rows, cols) each:
+
+        * ``direct``   ``irradiation(track directions, dni x hours)``: the beam on the local slope, shadows cast;
+        * ``diffuse``  ``sky_view_factor(azimuths) x sum(dhi x hours)``: an ISOTROPIC sky seen through the horizontal-surface
+          sky-view factor -- an approximation: the sky is brighter near the sun and the horizon, and a steep facet sees less
+          sky, and some ground, which this ignores;
+        * ``global``   their sum.
+
+        ``dni`` / ``dhi`` (W/m^2, (K,)) default to ``insolation.clear_sky`` of the track's elevations; measured values go in
+        instead.  ``irradiation_kwargs`` (horizontal, curved, terrain_only, lift, region) go to irradiation(); ``curved``,
+        ``lift`` and ``region`` to sky_view_factor() as well.  Host form."""
+        from . import insolation as _insolation
+
+        unknown = set(irradiation_kwargs) - {"horizontal", "curved", "terrain_only", "lift", "region"}
+        if unknown:
+            raise TypeError(f"insolation() got unexpected keyword arguments {sorted(unknown)}")
+        hours = np.asarray(track["hours"], np.float64)
+        if dni is None or dhi is None:
+            clear = _insolation.clear_sky(track["elevation_deg"])
+            dni = clear[0] if dni is None else dni
+            dhi = clear[1] if dhi is None else dhi
+        dni, dhi = np.asarray(dni, np.float64), np.asarray(dhi, np.float64)
+        direct = self.irradiation(np.asarray(track["directions"], np.float32), (dni * hours).astype(np.float32), **irradiation_kwargs)
+        sky = {k: v for k, v in irradiation_kwargs.items() if k in ("curved", "lift", "region")}
+        diffuse = (self.sky_view_factor(azimuths, **sky) * np.float32((dhi * hours).sum())).astype(np.float32)
+        return {"direct": direct, "diffuse": diffuse, "global": (direct + diffuse).astype(np.float32)}
 
     def certificates(self) -> dict:
         """Diagnostics (synchronises): content hashes of the sun-ray and primary-ray certificates."""

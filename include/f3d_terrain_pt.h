@@ -567,6 +567,51 @@ typedef struct f3d_session_horizon_desc {
     uint32_t reserved;      /* 0 */
 } f3d_session_horizon_desc;
 int f3d_session_horizon(f3d_session *session, const f3d_session_horizon_desc *desc, char *err, size_t errlen);
+/* ---- irradiation rasters: beam energy over a sun track ------------------------------------------------------------------------
+ * For every DEM sample of a region, the energy the direct beam delivers over a set of sun positions: each position weighted
+ * by its irradiance and by the cosine of incidence on the local slope, counted where the visibility rasters' ray toward it
+ * is unblocked (k_irradiation; the contract is at the head of csrc/f3d_irradiation.h).  All arithmetic is f32, one rounding
+ * per operation, no fma.  The sample stands on the lifted lattice point o of the visibility rasters.  Its gradient (gx, gz) is
+ * the central difference of the heights the session holds (exaggeration applied), one-sided on the DEM's border, over the
+ * lattice's own plane positions; q = (gx gx + gz gz) + 1; the unit normal is (-gx, 1, -gz) / sqrt(q).  HORIZONTAL: gx = gz = 0
+ * (the beam on a horizontal plane).  A direction is four f32 (x, y, z, weight): toward the sun, as given (need not be unit),
+ * and a weight >= 0 (W/m^2 x hours, say).  With l2 = (x x + y y) + z z, m = (y - gx x) - gz z and c = m / sqrt(q l2), the term
+ * counts when weight > 0, c > 0, the ray (o, (x, y, z), t in [0, 1e30]) is one the occlusion query marches and it is unblocked:
+ *   energy  rows * cols f32: the sum of weight * c over the terms that count, added in f32 for k = 0, 1, ...
+ *   count   rows * cols uint32: the number of terms that count
+ *   normal  rows * cols x 3 f32: the unit normal
+ * A facet turned away from the sun, a zero weight and a refused direction add nothing and march no ray.  Any output may be
+ * NULL, not all; with normal alone direction_count may be 0 and nothing marches.  TERRAIN_ONLY, CURVED, DEVICE_POINTERS,
+ * NO_WAIT and the ordering on the session stream are the raster's; nothing a frame launch reads is written.
+ *   host pointers (default)  blocking; staged through the visibility rasters' scratch buffer (the outputs asked for + 16 bytes
+ *       a direction), grown only for a larger call than any before, against memory_budget_bytes (too small: status 2, session
+ *       unchanged).  A non-finite component or a negative weight: refused
+ *   DEVICE_POINTERS          directions (16-byte aligned), energy, count and normal are device memory; nothing is copied or
+ *       allocated.  A non-finite component or a negative weight: that term is 0
+ * Refused (status 1, session unchanged): an unknown flag, reserved != 0, NO_WAIT without DEVICE_POINTERS, a region that is
+ * empty or reaches outside the DEM, a non-finite lift, all outputs NULL, direction_count 0 with energy or count asked for,
+ * NULL directions with direction_count > 0.  No ABI version bump: detected by the symbol f3d_session_irradiation. */
+#define F3D_IRRADIATION_TERRAIN_ONLY 1u
+#define F3D_IRRADIATION_CURVED 2u
+#define F3D_IRRADIATION_DEVICE_POINTERS 4u
+#define F3D_IRRADIATION_NO_WAIT 8u
+#define F3D_IRRADIATION_HORIZONTAL 16u
+typedef struct f3d_session_irradiation_desc {
+    uint32_t struct_size;     /* = sizeof(f3d_session_irradiation_desc) of the caller's header */
+    uint32_t flags;           /* F3D_IRRADIATION_TERRAIN_ONLY | _CURVED | _DEVICE_POINTERS | _NO_WAIT | _HORIZONTAL */
+    uint32_t row0;            /* the region, in DEM samples: rows [row0, row0 + rows), columns [col0, col0 + cols) */
+    uint32_t col0;
+    uint32_t rows;
+    uint32_t cols;
+    float lift;               /* added to every sample's height (the shadow rays' bias) */
+    uint32_t direction_count;
+    const float *directions;  /* direction_count x 4 f32: (x, y, z, weight) */
+    float *energy;            /* rows * cols, or NULL */
+    uint32_t *count;          /* rows * cols, or NULL */
+    float *normal;            /* rows * cols x 3, or NULL */
+    uint32_t reserved;        /* 0 */
+} f3d_session_irradiation_desc;
+int f3d_session_irradiation(f3d_session *session, const f3d_session_irradiation_desc *desc, char *err, size_t errlen);
 /* ---- drape: an image laid over the terrain, per-texel albedo ---------------------------------------------------------------
  * What an image changes on top of a re-aim, still without a new session: the albedo of TERRAIN hits.  The drape is
  * image[rows][cols] of linear RGB reflectances, f32, row-major, `channels` (3 or 4; a fourth channel is ignored) values a
