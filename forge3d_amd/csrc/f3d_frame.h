@@ -18,6 +18,7 @@
 #include "f3d_irradiation.h"
 #include "f3d_lds.h"
 #include "f3d_tiles.h"
+#include "f3d_skyblocks.h"
 
 namespace f3d {
 
@@ -628,6 +629,7 @@ __device__ __forceinline__ bool head_neighbourhood_empty(const FrameParams &P, u
     const uint32_t x_last = (x0 + 7u < P.cam.width ? x0 + 7u : P.cam.width - 1u), y_last = (y0 + 7u < P.band_end ? y0 + 7u : P.band_end - 1u);
     const uint32_t xa = x0 >= kSpatialReachLo ? x0 - kSpatialReachLo : 0u, ya = y0 >= kSpatialReachLo ? y0 - kSpatialReachLo : 0u;
     static_assert(8u + kSpatialReachLo + kSpatialReachHi <= 16u, "the 16 x 16 raster below covers the tile's reach");
+    static_assert(kSkyBlockMargin >= kSpatialReachLo && kSkyBlockMargin >= kSpatialReachHi, "a deep-sky block's margin covers the spatial pass");
     const uint32_t xb = x_last + kSpatialReachHi < P.cam.width ? x_last + kSpatialReachHi : P.cam.width - 1u;
     const uint32_t yb = y_last + kSpatialReachHi < P.cam.height ? y_last + kSpatialReachHi : P.cam.height - 1u;
     const uint32_t *words = reinterpret_cast<const uint32_t *>(P.res_in);
@@ -649,6 +651,17 @@ __global__ __launch_bounds__(kWave) void k_head(const FrameParams P) {
     uint32_t gx, gy, tile;
     const bool active = tile_pixel<1u>(P, gx, gy, tile);
     if (tile == 0xFFFFFFFFu) return;
+    // A deep-sky block (f3d_skyblocks.h; the wave's tile IS the block): settled here, not headed.  Every sample of every
+    // pixel is a miss under a uniform environment and every reservoir in reach is empty for good, so all a frame changes is
+    // the accumulation: the accumulation half of frame_tail with the sky tile's sum (frame_lanes), one lane a pixel.  No
+    // reservoir, head record or G-buffer word is touched (FrameParams::sky_blocks: the invariant), and the frame kernel
+    // does nothing for the block's tiles (frame_wave).  One uniform load.
+    if (P.sky_blocks != nullptr && (P.sky_blocks[tile] & kSkyBlockDeep) != 0u) {
+        float m2 = 0.0f;
+        if (active) m2 = frame_tail_accumulate(P, gx, gy, all_miss_radiance(P));
+        if (P.collect_stats != 0u) publish_window_stats(P, active, m2);
+        return;
+    }
 #if !defined(F3D_NO_EMPTY_HEAD)  // A/B + test-of-the-tests switch
     if (P.frame_index > 0u && head_neighbourhood_empty(P, gx, gy)) {
         if (active) {
@@ -676,9 +689,18 @@ __global__ __launch_bounds__(kWave) void k_head(const FrameParams P) {
 template <uint32_t S, bool MESH, bool DRAPE>
 __device__ __forceinline__ void frame_wave(const FrameParams &P, uint32_t *lds) {
     const unsigned long long t_start = wall_clock64();  // 100 MHz: the wave's cost for the next tile ordering
-    typename PendingFor<MESH>::type pend{make_pending(lds, P.terrain)};
     uint32_t gx = 0u, gy = 0u, tile;
     const bool active = tile_pixel<S>(P, gx, gy, tile, P.tile_order);
+    if constexpr (S != 1u) {
+        // A tile of a deep-sky block (f3d_skyblocks.h): k_head has settled its pixels, nothing is left to do.  One uniform
+        // load and a scalar branch in front of the LDS set-up; no tile cost is written -- it stays 0, the cheapest class.
+        if (P.sky_blocks != nullptr && tile != kNoTile) {
+            constexpr TileDims shape = tile_shape<S>();
+            const uint32_t block = sky_block_of_tile(tile, tiles_across(P.cam.width, shape), shape, tiles_across(P.cam.width, kSkyBlockShape));
+            if ((P.sky_blocks[block] & kSkyBlockDeep) != 0u) return;
+        }
+    }
+    typename PendingFor<MESH>::type pend{make_pending(lds, P.terrain)};
     float m2 = 0.0f;
     if constexpr (S == 1u) {
         if (active) m2 = frame_pixel<DRAPE>(P, gx, gy, pend);
@@ -710,6 +732,33 @@ template <int MIN_WAVES, uint32_t S, bool MESH>
 __global__ __launch_bounds__(kWave, MIN_WAVES) void k_frame_drape(const FrameParams P) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
     frame_wave<S, MESH, true>(P, lds);
+}
+
+// The deep-sky table of a strip (f3d_skyblocks.h): one wave a block, its lanes over the block's 16 x 16 rectangle, a ballot.
+// Runs behind every pass that writes primary_start (k_gbuffer, k_reaim).  The word of a block: kSkyBlockDeep, and from bit
+// kSkyBlockCountShift on how many of the block's own pixels hold the certificate (the diagnostic's sum,
+// f3d_session_sky_blocks); `enabled` = 0 leaves every block "not deep".
+struct SkyBlocksParams {
+    const uint2 *primary_start;  // owned rows x width; null: no pixel holds a certificate
+    uint32_t *blocks;            // one word a block
+    SkyBlockGeom geom;
+    uint32_t enabled;
+};
+__global__ __launch_bounds__(kWave) void k_sky_blocks(const SkyBlocksParams B) {
+    const uint32_t block = blockIdx.x;  // (the grid is the block count)
+    const auto certified = [&](uint32_t x, uint32_t y) {
+        return certified_sky(B.primary_start[(size_t)(y - B.geom.row_begin) * B.geom.width + x]);
+    };
+    bool clear = false, own = false;
+    if (B.primary_start != nullptr) {
+        if (B.enabled != 0u) clear = sky_block_lane_clear(B.geom, block, threadIdx.x, certified);
+        const uint32_t x = (block % tiles_across(B.geom.width, kSkyBlockShape)) * 8u + (threadIdx.x & 7u);
+        const uint32_t y = B.geom.row_begin + (block / tiles_across(B.geom.width, kSkyBlockShape)) * 8u + (threadIdx.x >> 3);
+        own = x < B.geom.width && y < B.geom.row_end && certified(x, y);
+    }
+    const bool deep = __ballot(!clear) == 0ull;
+    const uint32_t count = (uint32_t)__popcll(__ballot(own));
+    if (threadIdx.x == 0u) B.blocks[block] = (deep ? kSkyBlockDeep : 0u) | (count << kSkyBlockCountShift);
 }
 
 __global__ __launch_bounds__(kWave) void k_gbuffer(const FrameParams P, float4 *gbuffer_n, float *depth) {

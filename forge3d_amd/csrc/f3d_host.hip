@@ -31,6 +31,7 @@
 #include "f3d_setup.h"
 #include "f3d_tables.h"
 #include "f3d_tiles.h"
+#include "f3d_skyblocks.h"
 
 using namespace f3d;
 
@@ -192,6 +193,9 @@ struct f3d_session {
     // longest-first dispatch (f3d_kernels.hip k_tile_order): one-band sessions with the default tile map
     uint32_t *tile_cost = nullptr, *tile_order = nullptr;
     int64_t cost_frame = -1, order_frame = -1;  // newest frame whose wave durations are in tile_cost / went into tile_order
+    // deep-sky blocks (f3d_skyblocks.h): the table k_sky_blocks builds behind every pass that writes the primary-ray
+    // certificates; null: a session whose frames cannot use one (sky_blocks_in_use)
+    uint32_t *sky_blocks = nullptr;
     // frames in flight (f3d_kernels.hip k_trace / k_merge): record buffer for `fd_frames` frames; 0 = the fused path
     uint32_t fd_frames = 0;
     // wavefront form of the trace batches (f3d_kernels.hip k_wf_primary / k_wf_occl): occlusion rays through queues in HBM
@@ -229,6 +233,28 @@ void plan_bands(f3d_session &s, uint32_t want, uint32_t want_streams);
 void aether_sun_terms(AetherDev &A, const f3d_terrain_ref_desc &d) {
     A.sun_intensity = aether_clamp_scale(f_clamp(d.sun_intensity, 0.0f, 65504.0f));
     A.exposure = aether_clamp_scale(f_clamp(d.exposure, 0.0f, 65504.0f));
+}
+
+// Deep-sky blocks (f3d_skyblocks.h).  A session has a table when its frames go through k_head + k_frame as ONE band of
+// the fused path with primary-ray certificates: sample lanes, no frames in flight (nor their wavefront form), one band.
+// Its blocks can be deep when, besides, the frame kernel's sky tile could fire: a uniform environment and no mesh walk.
+// The second half is looked at where the table is built AND where a frame is enqueued (a re-mesh may change it; the
+// re-aim pass it ends in rebuilds the table).
+bool sky_blocks_wanted(const f3d_session &s) {
+    return s.params.primary_start != nullptr && s.params.sample_lanes > 1u && s.fd_frames == 0u && s.bands.size() == 1;
+}
+bool sky_blocks_in_use(const f3d_session &s) {
+    const FrameParams &P = s.params;
+    return s.sky_blocks != nullptr && (P.env.width == 0u || P.env.height == 0u) && P.mesh.traversal_mode != 0u;
+}
+// The table from the certificates as the session stream holds them now: behind k_gbuffer (create) and k_reaim (re-aim,
+// re-mesh, re-terrain).  A re-arm leaves the certificates, and the table, alone.
+void enqueue_sky_blocks(f3d_session &s) {
+    if (!s.sky_blocks) return;
+    FrameParams P = s.params;
+    P.row_begin = s.row_begin;
+    P.row_end = s.row_end;
+    hip_check(launch_sky_blocks(P, s.sky_blocks, sky_blocks_in_use(s), s.stream), "sky-block table kernel");
 }
 
 // same_sun: the two sun directions the frame head chooses between (wi, normalize(wi)) are the same bits
@@ -642,6 +668,11 @@ void session_init(f3d_session &s, const f3d_terrain_ref_desc &d, const f3d_sessi
     P.res_out = s.res[0];
     P.collect_stats = 0;
     hip_check(launch_gbuffer(P, s.gbuffer_n, s.depth, s.stream), "g-buffer pass");
+    // (after the budget gate, which it never trips: a session renders the same without the table, only slower)
+    if (const size_t bytes = (size_t)std::max(sky_block_count(P), 1u) * sizeof(uint32_t); sky_blocks_wanted(s) && s.mem.device_bytes + bytes <= s.budget) {
+        s.sky_blocks = (uint32_t *)s.mem.alloc(bytes, "deep-sky blocks");
+        enqueue_sky_blocks(s);
+    }
     if (s.fd_frames) {
         P.band_begin = s.row_begin;
         P.band_end = s.row_end;
@@ -714,8 +745,11 @@ void enqueue_band(f3d_session &s, f3d_session::Band &b, size_t index, uint32_t f
             if (nb.stream != b.stream) hip_check(hipStreamWaitEvent(b.stream, nb.done[(frame - 1u) & 1u], 0), "band wait");
         }
     }
+    // (one band whenever there is a table: the band is the strip, and its tiling the table's)
+    P.sky_blocks = sky_blocks_in_use(s) && b.begin == s.row_begin && b.end == s.row_end ? s.sky_blocks : nullptr;
     if (P.sample_lanes > 1u) hip_check(launch_head(P, b.stream), "frame head kernel");
     ordered_timed_launch(s, b.stream, frame, [&] { hip_check(launch_frame(P, s.variant, b.stream), "frame kernel"); });
+    P.sky_blocks = nullptr;
     if (piped) {
         hip_check(hipEventRecord(b.done[frame & 1u], b.stream), "band done");
         b.unjoined = true;
@@ -1329,6 +1363,39 @@ int f3d_session_certificates(f3d_session *s, uint64_t out[2]) {
         };
         out[0] = dev(s->params.sun_clear, px * sizeof(float2));
         out[1] = dev(s->params.primary_start, px * sizeof(uint2));
+        return F3D_STATUS_OK;
+    } catch (...) {
+        return F3D_STATUS_DEVICE;
+    }
+}
+
+// Diagnostics: the deep-sky blocks of the session (f3d_skyblocks.h) -- out = {blocks of the strip, deep blocks, pixels that
+// hold the sky certificate, pixels in deep blocks}.  A session whose frames use no table reports 0 deep blocks (and, without
+// a table at all, 0 certified pixels).  Synchronises.
+int f3d_session_sky_blocks(f3d_session *s, uint32_t out[4]) {
+    if (!s || !out) return F3D_STATUS_VALUE;
+    try {
+        DeviceGuard guard(s->device);
+        join_bands(*s);
+        hip_check(hipStreamSynchronize(s->stream), "sky blocks");
+        FrameParams P = s->params;
+        P.row_begin = s->row_begin;
+        P.row_end = s->row_end;
+        const uint32_t blocks = sky_block_count(P), blocks_x = tiles_across(s->width, kSkyBlockShape);
+        out[0] = blocks;
+        out[1] = out[2] = out[3] = 0u;
+        if (!s->sky_blocks || blocks == 0u) return F3D_STATUS_OK;
+        std::vector<uint32_t> words(blocks);
+        hip_check(hipMemcpy(words.data(), s->sky_blocks, (size_t)blocks * sizeof(uint32_t), hipMemcpyDeviceToHost), "sky-block download");
+        const bool in_use = sky_blocks_in_use(*s);
+        for (uint32_t b = 0; b < blocks; b++) {
+            out[2] += words[b] >> kSkyBlockCountShift;
+            if (in_use && (words[b] & kSkyBlockDeep) != 0u) {
+                const uint32_t x0 = (b % blocks_x) * 8u, y0 = (b / blocks_x) * 8u;  // (y0: from the strip's first row)
+                out[1]++;
+                out[3] += std::min(8u, s->width - x0) * std::min(8u, s->rows - y0);
+            }
+        }
         return F3D_STATUS_OK;
     } catch (...) {
         return F3D_STATUS_DEVICE;

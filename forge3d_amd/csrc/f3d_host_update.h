@@ -95,8 +95,12 @@ struct Update {
         R.res[1] = s.res[1];
         R.tile_cost = s.tile_cost;
         R.tiles = s.tile_cost ? frame_tile_count(P, nullptr) : 0u;
-        if (cam) hip_check(launch_reaim(R, s.stream), "re-aim kernel");
-        else hip_check(launch_rearm(R, s.stream), "re-arm kernel");
+        if (cam) {
+            hip_check(launch_reaim(R, s.stream), "re-aim kernel");
+            enqueue_sky_blocks(s);  // (new primary-ray certificates: the deep-sky table of the new view, f3d_skyblocks.h)
+        } else {
+            hip_check(launch_rearm(R, s.stream), "re-arm kernel");
+        }
         // host-side frame state as a new session has it
         s.cost_frame = s.order_frame = -1;
         s.rendered = false;

@@ -165,6 +165,15 @@ hipError_t launch_gbuffer(const FrameParams &p, float4 *gbuffer_n, float *depth,
     hipLaunchKernelGGL(k_gbuffer, dim3(frame_grid(p)), dim3(kWave), 0, stream, p, gbuffer_n, depth);
     return hipGetLastError();
 }
+static inline SkyBlockGeom sky_geom(const FrameParams &p) { return SkyBlockGeom{p.cam.width, p.cam.height, p.row_begin, p.row_end}; }
+uint32_t sky_block_count(const FrameParams &p) { return sky_block_grid(sky_geom(p)).count(); }
+hipError_t launch_sky_blocks(const FrameParams &p, uint32_t *blocks, bool enabled, hipStream_t stream) {
+    const uint32_t count = sky_block_count(p);
+    if (count == 0u || !blocks) return hipSuccess;
+    const SkyBlocksParams B{p.primary_start, blocks, sky_geom(p), enabled ? 1u : 0u};
+    hipLaunchKernelGGL(k_sky_blocks, dim3(count), dim3(kWave), 0, stream, B);
+    return hipGetLastError();
+}
 hipError_t launch_rearm(const RearmParams &p, hipStream_t stream) {
     if (frame_grid(p.frame) == 0u) return hipSuccess;
     hipLaunchKernelGGL(k_rearm, dim3(frame_grid(p.frame)), dim3(kWave), 0, stream, p);

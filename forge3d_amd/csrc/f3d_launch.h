@@ -40,6 +40,9 @@ hipError_t launch_trace_init(const FrameParams &p, hipStream_t stream);         
 uint32_t frame_tile_count(const FrameParams &p, uint32_t *grid);
 hipError_t launch_tile_order(const FrameParams &p, const uint32_t *cost, uint32_t *order, hipStream_t stream);
 hipError_t launch_gbuffer(const FrameParams &p, float4 *gbuffer_n, float *depth, hipStream_t stream);
+// the deep-sky table of the strip of p (f3d_skyblocks.h) from p.primary_start; enabled = false: every block "not deep"
+hipError_t launch_sky_blocks(const FrameParams &p, uint32_t *blocks, bool enabled, hipStream_t stream);
+uint32_t sky_block_count(const FrameParams &p);  // blocks of the strip of p
 hipError_t launch_rearm(const RearmParams &p, hipStream_t stream);  // same grid and pixel mapping as launch_gbuffer
 hipError_t launch_reaim(const RearmParams &p, hipStream_t stream);  // ... and its LDS: the G-buffer pass and the re-arm in one
 hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream);  // (a draped session: the draped resolve)

@@ -250,6 +250,12 @@ struct FrameParams {
     uint32_t *fix_count;  // [2]: running total (diagnostics)
     WfQueues wf;          // wavefront form of the trace batch (sun_o == null: k_trace traces the rays itself)
     const DrapeDev *drape;  // per-texel terrain albedo (null: none); read by the draped kernels only
+    // Deep-sky blocks (f3d_skyblocks.h; k_sky_blocks builds the table behind every pass that writes primary_start): one word
+    // per 8 x 8 block of the strip, bit 0 = deep; null: no block is.  k_head settles the pixels of a deep block
+    // (accumulation and Welford state only) and the frame kernel does nothing for its tiles.  INVARIANT: nothing reads head[]
+    // of a pixel in a deep block, and nothing writes a non-zero reservoir there -- both reservoir buffers of such a pixel
+    // stay at the zero the session's clear gave them, which is what the passes skipped would have written.
+    const uint32_t *sky_blocks;
 };
 F3D_HD uint32_t sample_lanes_of(const FrameParams &p) { return p.sample_lanes ? p.sample_lanes : 1u; }  // (0: unset, one lane)
 

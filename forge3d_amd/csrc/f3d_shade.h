@@ -895,17 +895,21 @@ F3D_HD V3 all_miss_radiance(const FrameParams &P) {
     return radiance;
 }
 
-// Everything after the sample loop (:549-574) plus the temporal pass; returns Welford m2.
-F3D_HD float frame_tail(const FrameParams &P, uint32_t gx, uint32_t gy, Reservoir cand, V3 radiance) {
-    const size_t lp = (size_t)(gy - P.row_begin) * P.cam.width + gx;
-    const float fspp = (float)P.spp;
-    radiance = V3{radiance.x / fspp, radiance.y / fspp, radiance.z / fspp};
+// Everything after the sample loop (:549-574) plus the temporal pass, in its two halves.
+// The reservoir half: the candidate's weight and the temporal merge with the history frame_head parked.
+F3D_HD void frame_tail_reservoir(const FrameParams &P, uint32_t gx, uint32_t gy, Reservoir cand) {
     if (cand.m > 0u && cand.w_sum > 0.0f && cand.target_pdf > 0.0f)
         cand.weight = restir_div(cand.w_sum, (float)cand.m * cand.target_pdf);
     const size_t ri = reservoir_index(P, gx, gy);
     const Reservoir prev = unpack(P.res_out[ri]);  // parked by frame_head
     P.res_out[ri] = pack(temporal_merge(prev, cand));
-
+}
+// The accumulation half: the samples' sum `radiance` into the accumulation and the Welford state; returns Welford m2.  All a
+// frame changes of a pixel in a deep-sky block (f3d_skyblocks.h), where k_head runs it with all_miss_radiance.
+F3D_HD float frame_tail_accumulate(const FrameParams &P, uint32_t gx, uint32_t gy, V3 radiance) {
+    const size_t lp = (size_t)(gy - P.row_begin) * P.cam.width + gx;
+    const float fspp = (float)P.spp;
+    radiance = V3{radiance.x / fspp, radiance.y / fspp, radiance.z / fspp};
     float4 am = P.accum_mean[lp];
     float wf_m2 = P.welford_m2[lp];
     float wf_mean = am.w;
@@ -924,6 +928,10 @@ F3D_HD float frame_tail(const FrameParams &P, uint32_t gx, uint32_t gy, Reservoi
     P.accum_mean[lp] = float4{acc.x, acc.y, acc.z, mean};
     P.welford_m2[lp] = m2;
     return m2;
+}
+F3D_HD float frame_tail(const FrameParams &P, uint32_t gx, uint32_t gy, Reservoir cand, V3 radiance) {
+    frame_tail_reservoir(P, gx, gy, cand);
+    return frame_tail_accumulate(P, gx, gy, radiance);
 }
 
 // ---- frames in flight: the per-pixel pieces (f3d_kernels.hip k_trace / k_merge / k_fix) -----------

@@ -822,6 +822,14 @@ class TerrainSession:
             raise RuntimeError("f3d_session_certificates failed")
         return {"sun_clear": int(out[0]), "primary_start": int(out[1])}
 
+    def sky_blocks(self) -> dict:
+        """Diagnostics (synchronises): the session's deep-sky blocks -- 8 x 8 pixel blocks so far inside certified sky that
+        a frame only accumulates there.  0 deep blocks for a session whose frames use no such table."""
+        out = (C.c_uint32 * 4)()
+        if self._lib.f3d_session_sky_blocks(self._handle, out) != 0:
+            raise RuntimeError("f3d_session_sky_blocks failed")
+        return {"blocks": int(out[0]), "deep_blocks": int(out[1]), "certified_pixels": int(out[2]), "deep_pixels": int(out[3])}
+
     # -- stepping ---------------------------------------------------------------------
     def enqueue_frames(self, first_frame: int, count: int, collect_stats: bool = False):
         """Asynchronously enqueue accumulation frames on the session stream."""

@@ -337,6 +337,11 @@ int f3d_session_rearm(f3d_session *session, const f3d_session_rearm_desc *desc, 
 int f3d_session_render(f3d_session *session, f3d_terrain_ref_out *out, char *err, size_t errlen);
 /* Diagnostics (synchronises): content hashes of the sun-ray (out[0]) and primary-ray (out[1]) certificates. */
 int f3d_session_certificates(f3d_session *session, uint64_t out[2]);
+/* Diagnostics (synchronises): the deep-sky blocks of the session -- 8 x 8 pixel blocks whose pixels, and every pixel
+ * within 4 of them, hold the sky certificate; a frame only accumulates there.  out = {blocks of the strip, deep blocks,
+ * pixels that hold the sky certificate, pixels in deep blocks}.  0 deep blocks for a session whose frames use no such
+ * table: an environment map, a mesh walk, one sample lane, frames in flight, more than one band. */
+int f3d_session_sky_blocks(f3d_session *session, uint32_t out[4]);
 /* ---- re-aim: a re-arm under a new camera ------------------------------------------------------------------------
  * What a new camera changes on top of a re-arm, still without a new session: the camera uniforms (all of them, the
  * pixel cone included), and everything the create's G-buffer pass writes -- normals and hit kind, depth, primary-ray
