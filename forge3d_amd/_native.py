@@ -204,6 +204,20 @@ class IrradiationDesc(C.Structure):
 IRRADIATION_TERRAIN_ONLY, IRRADIATION_CURVED, IRRADIATION_DEVICE_POINTERS, IRRADIATION_NO_WAIT, IRRADIATION_HORIZONTAL = 1, 2, 4, 8, 16
 
 
+class ClearanceDesc(C.Structure):
+    """f3d_session_clearance_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("observer_count", C.c_uint32),
+        ("observers", C.c_void_p), ("height", C.c_void_p), ("lowest", C.c_void_p),
+        ("reserved", C.c_uint32),
+    ]
+
+
+CLEARANCE_CURVED, CLEARANCE_DEVICE_POINTERS, CLEARANCE_NO_WAIT = 2, 4, 8
+
+
 class DrapeDesc(C.Structure):
     """f3d_session_drape_desc"""
     _fields_ = [
@@ -264,6 +278,7 @@ ABI = [
     ("f3d_session_raster", C.c_int, [C.c_void_p, _P(RasterDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_horizon", C.c_int, [C.c_void_p, _P(HorizonDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_irradiation", C.c_int, [C.c_void_p, _P(IrradiationDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_clearance", C.c_int, [C.c_void_p, _P(ClearanceDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape", C.c_int, [C.c_void_p, _P(DrapeDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),

@@ -16,6 +16,7 @@
 #include "f3d_raster.h"
 #include "f3d_horizon.h"
 #include "f3d_irradiation.h"
+#include "f3d_clearance.h"
 #include "f3d_lds.h"
 #include "f3d_tiles.h"
 #include "f3d_skyblocks.h"
@@ -920,6 +921,41 @@ __global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
         sum = sum + horizon_sky_term(H, az.x, az.y);
     }
     if (R.sky_view) R.sky_view[n] = 1.0f - sum / (float)R.azimuth_count;
+}
+
+// Clearance rasters on a live session (f3d_session_clearance; f3d_clearance.h): k_horizon's shape -- one wave a workgroup, one
+// lane a DEM sample of the region (64 consecutive samples, or with R.block an 8 x 8 block: measured, profiles/README.md), the
+// band table's per-level layout in 128 bytes of LDS.  The loop over the observers is wave-uniform and every lane reads the
+// observer at the same address; the lane keeps its sample and the minimum over the observers in registers and writes what it
+// owns with ordinary stores.  With height null nothing of size observer_count x rows * cols exists anywhere.
+__global__ __launch_bounds__(kWave) void k_clearance(const ClearanceParams R) {
+    __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
+    if (threadIdx.x < kMaxLevels) {
+        table[2u * threadIdx.x] = R.terrain.band_offset[threadIdx.x];
+        table[2u * threadIdx.x + 1u] = R.terrain.band_shift[threadIdx.x];
+    }
+    __syncthreads();
+    const HorizonLevels levels{table};
+    const uint32_t total = R.rows * R.cols;
+    uint32_t n = blockIdx.x * kWave + threadIdx.x;
+    bool have = n < total;
+    if (R.block != 0u) {
+        const uint32_t tiles_x = (R.cols + 7u) >> 3;
+        const uint32_t r = (blockIdx.x / tiles_x) * 8u + (threadIdx.x >> 3), c = (blockIdx.x % tiles_x) * 8u + (threadIdx.x & 7u);
+        have = r < R.rows && c < R.cols;
+        n = r * R.cols + c;
+    }
+    if (!have) return;  // (no wave primitive below)
+    uint32_t i, j;
+    const V3 g = clearance_sample(R, n, i, j);
+    float lowest = __builtin_inff();
+    for (uint32_t k = 0u; k < R.observer_count; k++) {
+        const float4 observer = R.observers[k];
+        const float L = clearance_height(R, g, i, j, observer, levels);
+        if (R.height) R.height[(size_t)k * total + n] = L;
+        lowest = f_min(lowest, L);  // (a NaN plane is ignored)
+    }
+    if (R.lowest) R.lowest[n] = lowest;
 }
 
 // Irradiation rasters on a live session (f3d_session_irradiation; f3d_irradiation.h): k_raster's shape -- one wave a

@@ -1005,6 +1005,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 #include "f3d_host_raster.h"  // DEM visibility rasters on a live session: checks, scratch, staged copies, launch and their C ABI
 #include "f3d_host_horizon.h"  // horizon rasters on a live session: checks, the raster scratch, staged copies, launch and their C ABI
 #include "f3d_host_irradiation.h"  // irradiation rasters on a live session: checks, the raster scratch, staged copies, launch and their C ABI
+#include "f3d_host_clearance.h"  // clearance rasters on a live session: checks, the raster scratch, staged copies, launch and their C ABI
 #include "f3d_host_drape.h"  // an image draped over the terrain of a live session: checks, buffer, staged upload, packing and its C ABI
 
 // ---------------------------------------------------------------------------------------

@@ -333,4 +333,18 @@ struct IrradiationParams {
     float *normal;               // rows * cols x 3: the unit normal the cosine is taken against
 };
 
+// Clearance rasters on a live session (f3d_session_clearance; k_clearance, f3d_clearance.h): terrain only, one lane a DEM
+// sample of the region, a loop over the observers.  Either output may be null.
+struct ClearanceParams {
+    TerrainDev terrain;
+    uint32_t curved;             // the sight lines' curvature policy, as a TOWARD_POINT raster's
+    uint32_t row0, col0, rows, cols;  // the region, as a raster's
+    uint32_t observer_count;     // >= 1
+    uint32_t step_cap;           // clearance_step_cap(terrain)
+    uint32_t block;              // a wave's footprint: 0 = 64 consecutive samples of the region, 1 = an 8 x 8 block of it
+    const float4 *observers;     // (x, Y, z, w) each
+    float *height;               // observer_count x rows * cols
+    float *lowest;               // rows * cols: the minimum over the observers
+};
+
 }  // namespace f3d

@@ -679,6 +679,94 @@ class TerrainSession:
         are never materialised, on the device or here.  Arguments as horizon()."""
         return self._horizon(azimuths, lift, curved, region, False, True, wait)[1]
 
+    # -- clearance rasters: the height needed to be seen --------------------------------------
+    def clearance(self, observers, *, curved: bool = False, region=None, planes: bool = True, lowest: bool = False, wait: bool = True):
+        """One f3d_session_clearance: for every DEM sample of ``region`` (``(row0, col0, rows, cols)``, default the whole DEM)
+        and every observer, how far above the ground a target over the sample must stand for the observer to see it -- the
+        smallest ``lift`` at which ``visibility(observer, toward=True, lift=lift, terrain_only=True)`` answers True, as an
+        exact max-slope walk of the session's min/max pyramid (terrain only: a mesh hides nothing here).  ``observers``
+        (K, 4) float32 rows ``(x, y, z, w)`` ((K, 3): w = 0): a world position and, for ``w > 0``, a maximum horizontal
+        distance.  0: the ground itself shows; +inf: out of range, or the observer lies under the surface; NaN: a non-finite
+        observer handed in as a tensor.  ``curved``: the sight lines follow the session's earth curvature, as visibility()'s.
+        A NumPy array takes the host form (blocking); a torch tensor on the session's device the device form (results are
+        tensors; ``wait=False`` returns with the kernel in flight on the session's stream).
+        Returns the float32 array (K, rows, cols) for ``planes``, the float32 array (rows, cols) of the minimum over the
+        observers ("seen by any of them"; the K planes are then never materialised) for ``lowest``, ``(planes, lowest)`` for
+        both.  ``viewshed(obs, target_height=th) == (visible_height(obs) < th + SURFACE_BIAS)`` away from a band of rounding
+        around the threshold."""
+        if not (planes or lowest):
+            raise ValueError("clearance() needs an output: planes, lowest or both")
+        dem_h, dem_w = self.dem_shape
+        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
+        if min(row0, col0, rows, cols) < 0:
+            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        q = _native.ClearanceDesc()
+        q.struct_size = C.sizeof(_native.ClearanceDesc)
+        q.flags = _native.CLEARANCE_CURVED if curved else 0
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        if type(observers).__module__.split(".")[0] == "torch":
+            import torch  # (only for callers who hand tensors in)
+
+            if not observers.is_cuda:
+                raise ValueError("a tensor clearance needs a tensor on the session's device (NumPy arrays take the host form)")
+            t = observers.to(torch.float32)
+            if t.ndim != 2 or t.shape[1] not in (3, 4):
+                raise ValueError(f"expected shape (K, 4) or (K, 3), got {tuple(observers.shape)}")
+            if t.shape[1] == 3:
+                t = torch.cat([t, torch.zeros_like(t[:, :1])], 1)
+            t = t.contiguous()
+            k = int(t.shape[0])
+            q.flags |= _native.CLEARANCE_DEVICE_POINTERS | (0 if wait else _native.CLEARANCE_NO_WAIT)
+            h_out = torch.empty((k, rows, cols), dtype=torch.float32, device=t.device) if planes else None
+            l_out = torch.empty((rows, cols), dtype=torch.float32, device=t.device) if lowest else None
+            q.observer_count, q.observers = k, (t.data_ptr() if k else None)
+            q.height, q.lowest = (h_out.data_ptr() if planes else None), (l_out.data_ptr() if lowest else None)
+        else:
+            if not wait:
+                raise ValueError("wait=False is for tensor clearances: results in host memory are there when the call returns")
+            t = np.asarray(observers, dtype=np.float32)
+            if t.ndim != 2 or t.shape[1] not in (3, 4):
+                raise ValueError(f"expected shape (K, 4) or (K, 3), got {t.shape}")
+            if t.shape[1] == 3:
+                t = np.concatenate([t, np.zeros((t.shape[0], 1), np.float32)], 1)
+            t = np.ascontiguousarray(t)
+            k = int(t.shape[0])
+            h_out = np.zeros((k, rows, cols), np.float32) if planes else None
+            l_out = np.zeros((rows, cols), np.float32) if lowest else None
+            q.observer_count, q.observers = k, (t.ctypes.data if k else None)
+            q.height, q.lowest = (h_out.ctypes.data if planes else None), (l_out.ctypes.data if lowest else None)
+        self._check(self._lib.f3d_session_clearance(self._handle, C.byref(q), self._err, len(self._err)))  # (t lives until here)
+        return (h_out, l_out) if (planes and lowest) else (h_out if planes else l_out)
+
+    def visible_height(self, observer, *, observer_height: float = 1.7, max_distance=None, curved: bool = False, region=None):
+        """How high above the ground must a target over each DEM sample stand to be seen by at least one observer?  The
+        "above ground level" raster of a GIS viewshed: one pass is viewshed() for every ``target_height`` at once.
+        ``observer``: viewshed()'s forms -- ``(x, y, z)``, an absolute position, or ``(x, z)``, standing ``observer_height``
+        above ground(), or an (M, 3) / (M, 2) array of them.  ``max_distance``: samples farther away horizontally are never
+        seen.  Returns the float32 array (rows, cols): 0 where the ground itself shows, +inf where the sample is out of
+        range or no observer has ground under it (then every sample is +inf, as viewshed() sees nothing).
+        ``viewshed(obs, target_height=th) == (visible_height(obs) < th + SURFACE_BIAS)`` away from a band of rounding around
+        the threshold (terrain only: a mesh hides nothing here)."""
+        obs = np.asarray(observer, dtype=np.float32)
+        obs = np.atleast_2d(obs)
+        if obs.ndim != 2 or obs.shape[1] not in (2, 3):
+            raise ValueError(f"observer must be (x, y, z), (x, z) or an array of them, got shape {np.asarray(observer).shape}")
+        if obs.shape[1] == 2:
+            y = self.ground(obs) + np.float32(observer_height)  # (the terrain: an observer does not stand on the mesh)
+            obs = np.stack([obs[:, 0], y.astype(np.float32), obs[:, 1]], 1)
+            obs = obs[np.isfinite(obs).all(1)]  # (no ground under it: nothing to stand on, nothing seen)
+        w = np.float32(0.0 if max_distance is None else max_distance)
+        if max_distance is not None and not w > 0.0:
+            raise ValueError(f"max_distance must be positive, got {max_distance}")
+        if len(obs) == 0:
+            dem_h, dem_w = self.dem_shape
+            row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
+            if min(row0, col0) < 0 or min(rows, cols) <= 0 or row0 + rows > dem_h or col0 + cols > dem_w:
+                raise ValueError(f"region=(row0, col0, rows, cols)={tuple(region)} is empty or reaches outside the {dem_h}x{dem_w} DEM")
+            return np.full((rows, cols), np.inf, np.float32)
+        observers = np.concatenate([obs, np.full((len(obs), 1), w, np.float32)], 1).astype(np.float32)
+        return self.clearance(observers, curved=curved, region=region, planes=False, lowest=True)
+
     # -- irradiation rasters: beam energy over a sun track, surface normals --------------------
     @staticmethod
     def irradiation_terms(directions, weights=None):

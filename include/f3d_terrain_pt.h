@@ -617,6 +617,50 @@ typedef struct f3d_session_irradiation_desc {
     uint32_t reserved;        /* 0 */
 } f3d_session_irradiation_desc;
 int f3d_session_irradiation(f3d_session *session, const f3d_session_irradiation_desc *desc, char *err, size_t errlen);
+/* ---- clearance rasters: the height needed to be seen ---------------------------------------------------------------------------
+ * For every DEM sample of a region and every observer, how far above the GROUND a target over that sample must stand for
+ * the observer to see it -- the "above ground level" output of a GIS viewshed: one pass is the viewshed for every target
+ * height at once (terrain only: a session with a mesh answers for its terrain).  One bounded max-slope walk of the min/max
+ * pyramid per sample per observer, from the observer (k_clearance; the contract, the leaf's closed form and the bound are at
+ * the head of csrc/f3d_clearance.h).  The sample's lattice point g = (g.x, h, g.z) is the visibility rasters' with lift 0; an
+ * observer is four f32 (x, Y, z, w) as a TOWARD_POINT target of f3d_session_raster, w > 0 a maximum horizontal distance.  With
+ * dx = x - g.x, dz = z - g.z, hd2 = dx dx + dz dz, k = hd2 inv_two_r_prime with CURVED on a scene with earth curvature (else 0),
+ * p(t) = (g.x + t dx, g.z + t dz) and y the bilinear surface,
+ *     L* = sup over t in (0, 1), p(t) inside the footprint, of (y(p(t)) - t Y) / (1 - t) + k t - h
+ * is the smallest lift at which the TOWARD_POINT raster's ray from the sample is unblocked, and the value is max(L*, +0).
+ *   +inf  hd2 > w w; the observer under the surface; the sample straight over the observer (hd2 == 0 and Y < h)
+ *   0     the ground itself shows: no terrain between, or none high enough; hd2 == 0 and Y >= h
+ *   NaN   a walk that exceeds its step cap (no DEM does); a non-finite observer component in the device form
+ * All arithmetic is f32, one rounding per operation.
+ *   height  observer_count x rows * cols f32: plane k is observer k, sample n = r * cols + c
+ *   lowest  rows * cols f32: the minimum over the observers ("seen by any of them"), NaN planes ignored
+ * Either may be NULL, not both; with height NULL nothing of size observer_count x rows * cols is written or allocated.
+ * CURVED, DEVICE_POINTERS, NO_WAIT and the ordering on the session stream are the raster's; nothing a frame launch reads is
+ * written.
+ *   host pointers (default)  blocking; staged through the visibility rasters' scratch buffer (the outputs asked for + 16 bytes
+ *       an observer), grown only for a larger call than any before, against memory_budget_bytes (too small: status 2, session
+ *       unchanged).  A non-finite observer component or a negative w: refused
+ *   DEVICE_POINTERS          observers (16-byte aligned), height and lowest are device memory; nothing is copied or allocated.
+ * Refused (status 1, session unchanged): an unknown flag, reserved != 0, NO_WAIT without DEVICE_POINTERS, a region that is
+ * empty or reaches outside the DEM, observer_count 0, NULL observers, both outputs NULL.  No ABI version bump: detected by
+ * the symbol f3d_session_clearance. */
+#define F3D_CLEARANCE_CURVED 2u
+#define F3D_CLEARANCE_DEVICE_POINTERS 4u
+#define F3D_CLEARANCE_NO_WAIT 8u
+typedef struct f3d_session_clearance_desc {
+    uint32_t struct_size;     /* = sizeof(f3d_session_clearance_desc) of the caller's header */
+    uint32_t flags;           /* F3D_CLEARANCE_CURVED | _DEVICE_POINTERS | _NO_WAIT */
+    uint32_t row0;            /* the region, in DEM samples: rows [row0, row0 + rows), columns [col0, col0 + cols) */
+    uint32_t col0;
+    uint32_t rows;
+    uint32_t cols;
+    uint32_t observer_count;  /* >= 1 */
+    const float *observers;   /* observer_count x 4 f32: (x, Y, z, w) */
+    float *height;            /* observer_count x rows * cols, or NULL */
+    float *lowest;            /* rows * cols, or NULL */
+    uint32_t reserved;        /* 0 */
+} f3d_session_clearance_desc;
+int f3d_session_clearance(f3d_session *session, const f3d_session_clearance_desc *desc, char *err, size_t errlen);
 /* ---- drape: an image laid over the terrain, per-texel albedo ---------------------------------------------------------------
  * What an image changes on top of a re-aim, still without a new session: the albedo of TERRAIN hits.  The drape is
  * image[rows][cols] of linear RGB reflectances, f32, row-major, `channels` (3 or 4; a fourth channel is ignored) values a
