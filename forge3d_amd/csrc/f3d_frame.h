@@ -893,24 +893,34 @@ struct HorizonLevels {
         shift = e.y;
     }
 };
-__global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
-    __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
+// The opening k_horizon and k_clearance share.  The band table's per-level layout into the workgroup's 128 bytes of LDS:
+__device__ __forceinline__ void load_level_table(uint32_t *table, const TerrainDev &terrain) {
     if (threadIdx.x < kMaxLevels) {
-        table[2u * threadIdx.x] = R.terrain.band_offset[threadIdx.x];
-        table[2u * threadIdx.x + 1u] = R.terrain.band_shift[threadIdx.x];
+        table[2u * threadIdx.x] = terrain.band_offset[threadIdx.x];
+        table[2u * threadIdx.x + 1u] = terrain.band_shift[threadIdx.x];
     }
     __syncthreads();
+}
+// (workgroup, lane) -> sample n of a rows x cols region: 64 consecutive samples a wave, or with `block` an 8 x 8 block of
+// the region.  false: the lane has no sample.
+__device__ __forceinline__ bool lane_sample(uint32_t rows, uint32_t cols, uint32_t block, uint32_t &n) {
+    n = blockIdx.x * kWave + threadIdx.x;
+    bool have = n < rows * cols;
+    if (block != 0u) {
+        const uint32_t tiles_x = (cols + 7u) >> 3;
+        const uint32_t r = (blockIdx.x / tiles_x) * 8u + (threadIdx.x >> 3), c = (blockIdx.x % tiles_x) * 8u + (threadIdx.x & 7u);
+        have = r < rows && c < cols;
+        n = r * cols + c;
+    }
+    return have;
+}
+__global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
+    __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
+    load_level_table(table, R.terrain);
     const HorizonLevels levels{table};
     const uint32_t total = R.rows * R.cols;
-    uint32_t n = blockIdx.x * kWave + threadIdx.x;
-    bool have = n < total;
-    if (R.block != 0u) {
-        const uint32_t tiles_x = (R.cols + 7u) >> 3;
-        const uint32_t r = (blockIdx.x / tiles_x) * 8u + (threadIdx.x >> 3), c = (blockIdx.x % tiles_x) * 8u + (threadIdx.x & 7u);
-        have = r < R.rows && c < R.cols;
-        n = r * R.cols + c;
-    }
-    if (!have) return;  // (no wave primitive below)
+    uint32_t n;
+    if (!lane_sample(R.rows, R.cols, R.block, n)) return;  // (no wave primitive below)
     uint32_t i, j;
     const V3 o = horizon_origin(R, n, i, j);
     float sum = 0.0f;
@@ -930,22 +940,11 @@ __global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
 // owns with ordinary stores.  With height null nothing of size observer_count x rows * cols exists anywhere.
 __global__ __launch_bounds__(kWave) void k_clearance(const ClearanceParams R) {
     __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
-    if (threadIdx.x < kMaxLevels) {
-        table[2u * threadIdx.x] = R.terrain.band_offset[threadIdx.x];
-        table[2u * threadIdx.x + 1u] = R.terrain.band_shift[threadIdx.x];
-    }
-    __syncthreads();
+    load_level_table(table, R.terrain);
     const HorizonLevels levels{table};
     const uint32_t total = R.rows * R.cols;
-    uint32_t n = blockIdx.x * kWave + threadIdx.x;
-    bool have = n < total;
-    if (R.block != 0u) {
-        const uint32_t tiles_x = (R.cols + 7u) >> 3;
-        const uint32_t r = (blockIdx.x / tiles_x) * 8u + (threadIdx.x >> 3), c = (blockIdx.x % tiles_x) * 8u + (threadIdx.x & 7u);
-        have = r < R.rows && c < R.cols;
-        n = r * R.cols + c;
-    }
-    if (!have) return;  // (no wave primitive below)
+    uint32_t n;
+    if (!lane_sample(R.rows, R.cols, R.block, n)) return;  // (no wave primitive below)
     uint32_t i, j;
     const V3 g = clearance_sample(R, n, i, j);
     float lowest = __builtin_inff();

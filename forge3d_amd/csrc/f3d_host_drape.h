@@ -13,9 +13,7 @@ void session_drape(f3d_session &s, const f3d_session_drape_desc &q) {
     Update u(s, q.aim.arm, &q.aim, "draped");
     if (q.flags & ~(kDrapeDevicePointers | kDrapeNoWait | kDrapePatch))
         fail(F3D_STATUS_VALUE, "unknown drape flags 0x%x (4 DEVICE_POINTERS, 8 NO_WAIT, 16 PATCH)", q.flags);
-    const bool device_form = (q.flags & kDrapeDevicePointers) != 0u, patch = (q.flags & kDrapePatch) != 0u;
-    if ((q.flags & kDrapeNoWait) && !device_form)
-        fail(F3D_STATUS_VALUE, "NO_WAIT needs DEVICE_POINTERS: an image in host memory has been read when the call returns");
+    const bool device_form = check_no_wait(q.flags, "an image in host memory has been read"), patch = (q.flags & kDrapePatch) != 0u;
     f3d_session::Drape &D = s.drape;
     if (q.image) {
         if (s.fd_frames)

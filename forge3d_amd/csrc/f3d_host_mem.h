@@ -331,6 +331,34 @@ void upload_staged(void *dst, const void *src, size_t bytes, hipStream_t stream,
     hip_check(hipEventSynchronize(pair.drained[1]), "upload");
 }
 
+// Device -> host through the library's pinned staging pair, in stream order behind everything enqueued on `stream`: the
+// mirror of upload_staged.  Returns when the bytes are in dst.
+void download_staged(void *dst, const void *src, size_t bytes, hipStream_t stream) {
+    constexpr size_t kChunk = 4u << 20;
+    StagingPair &pair = staging_for_current_device();
+    std::lock_guard<std::mutex> lock(pair.mutex);
+    for (int i = 0; i < 2; i++)
+        if (!pair.buffer[i]) {
+            hip_check(hipHostMalloc(&pair.buffer[i], kChunk, hipHostMallocPortable), "pinned staging buffer");
+            hip_check(hipEventCreateWithFlags(&pair.drained[i], hipEventDisableTiming), "staging event");
+        }
+    const size_t chunks = (bytes + kChunk - 1u) / kChunk;
+    for (size_t k = 0; k <= chunks; k++) {  // chunk k goes on its way, then chunk k - 1 is taken out of the other buffer
+        const int turn = (int)(k & 1u);
+        if (k < chunks) {
+            const size_t n = std::min(kChunk, bytes - k * kChunk);
+            hip_check(hipEventSynchronize(pair.drained[turn]), "staging buffer");  // (an upload that still reads it)
+            hip_check(hipMemcpyAsync(pair.buffer[turn], (const char *)src + k * kChunk, n, hipMemcpyDeviceToHost, stream), "download");
+            hip_check(hipEventRecord(pair.drained[turn], stream), "staging event");
+        }
+        if (k >= 1u) {
+            const size_t at = (k - 1u) * kChunk, m = std::min(kChunk, bytes - at);
+            hip_check(hipEventSynchronize(pair.drained[turn ^ 1]), "download");
+            memcpy((char *)dst + at, pair.buffer[turn ^ 1], m);
+        }
+    }
+}
+
 std::shared_ptr<CachedTables> acquire_tables(int device, const float *heights, uint32_t w, uint32_t h, float exaggeration,
                                              hipStream_t stream, bool *was_cached, const DemFingerprint *known = nullptr) {
     const uint64_t bytes = (uint64_t)w * h * sizeof(float);

@@ -4,47 +4,16 @@
 
 namespace {
 
-constexpr uint32_t kQueryTerrainOnly = 1u, kQueryCurved = 2u, kQueryDevicePointers = 4u, kQueryNoWait = 8u;
+constexpr uint32_t kQueryTerrainOnly = F3D_QUERY_TERRAIN_ONLY, kQueryCurved = F3D_QUERY_CURVED;
 // The host form's scratch holds, per ray, the widest input (8 f32) and every output (kind, t, normal, position,
 // primitive, direction: 12 words) whichever of them the caller asks for: its size is a function of `count` alone.
 constexpr size_t kQueryInBytes = 32u, kQueryOutWords = 12u, kQueryRayBytes = kQueryInBytes + 4u * kQueryOutWords;
 
-// Device -> host through the library's pinned staging pair, in stream order behind everything enqueued on `stream`: the
-// mirror of upload_staged.  Returns when the bytes are in dst.
-void download_staged(void *dst, const void *src, size_t bytes, hipStream_t stream) {
-    constexpr size_t kChunk = 4u << 20;
-    StagingPair &pair = staging_for_current_device();
-    std::lock_guard<std::mutex> lock(pair.mutex);
-    for (int i = 0; i < 2; i++)
-        if (!pair.buffer[i]) {
-            hip_check(hipHostMalloc(&pair.buffer[i], kChunk, hipHostMallocPortable), "pinned staging buffer");
-            hip_check(hipEventCreateWithFlags(&pair.drained[i], hipEventDisableTiming), "staging event");
-        }
-    const size_t chunks = (bytes + kChunk - 1u) / kChunk;
-    for (size_t k = 0; k <= chunks; k++) {  // chunk k goes on its way, then chunk k - 1 is taken out of the other buffer
-        const int turn = (int)(k & 1u);
-        if (k < chunks) {
-            const size_t n = std::min(kChunk, bytes - k * kChunk);
-            hip_check(hipEventSynchronize(pair.drained[turn]), "staging buffer");  // (an upload that still reads it)
-            hip_check(hipMemcpyAsync(pair.buffer[turn], (const char *)src + k * kChunk, n, hipMemcpyDeviceToHost, stream), "download");
-            hip_check(hipEventRecord(pair.drained[turn], stream), "staging event");
-        }
-        if (k >= 1u) {
-            const size_t at = (k - 1u) * kChunk, m = std::min(kChunk, bytes - at);
-            hip_check(hipEventSynchronize(pair.drained[turn ^ 1]), "download");
-            memcpy((char *)dst + at, pair.buffer[turn ^ 1], m);
-        }
-    }
-}
-
 void session_query(f3d_session &s, const f3d_session_query_desc &q) {
     check_struct_size(q, "f3d_session_query_desc");
     if (q.mode > 2u) fail(F3D_STATUS_VALUE, "query mode must be 0 (closest hit), 1 (occlusion) or 2 (pixels of the current camera), got %u", q.mode);
-    if (q.flags & ~(kQueryTerrainOnly | kQueryCurved | kQueryDevicePointers | kQueryNoWait))
-        fail(F3D_STATUS_VALUE, "unknown query flags 0x%x (1 TERRAIN_ONLY, 2 CURVED, 4 DEVICE_POINTERS, 8 NO_WAIT)", q.flags);
-    const bool device_form = (q.flags & kQueryDevicePointers) != 0u;
-    if ((q.flags & kQueryNoWait) && !device_form)
-        fail(F3D_STATUS_VALUE, "NO_WAIT needs DEVICE_POINTERS: results in host memory are there when the call returns");
+    check_flags(q.flags, kQueryTerrainOnly | kQueryCurved | kDevicePointers | kNoWait, "query", "1 TERRAIN_ONLY, 2 CURVED, 4 DEVICE_POINTERS, 8 NO_WAIT");
+    const bool device_form = check_no_wait(q.flags);
     if ((q.flags & kQueryCurved) && q.mode != 1u)
         fail(F3D_STATUS_VALUE, "CURVED is the sun rays' curvature policy of an occlusion query (mode 1); mode %u traces with curvature off", q.mode);
     if (q.mode == 1u && (q.t || q.normal || q.position || q.primitive || q.direction))
@@ -78,21 +47,11 @@ void session_query(f3d_session &s, const f3d_session_query_desc &q) {
         Q.direction = q.direction;
         join_bands(s);
         hip_check(launch_query(Q, s.stream), "query kernel");
-        if (!(q.flags & kQueryNoWait)) hip_check(hipStreamSynchronize(s.stream), "query");
+        if (!(q.flags & kNoWait)) hip_check(hipStreamSynchronize(s.stream), "query");
         return;
     }
     // host form: the session's scratch, grown only for a larger batch than any before
-    if (n > s.query_capacity) {
-        const uint64_t want = (uint64_t)n * kQueryRayBytes;
-        check_budget(s, s.mem.device_bytes - s.query_bytes + want, "ray query", "the scratch of this batch brings");
-        Ledger::Take take{s.mem};
-        void *fresh = take((size_t)want, "query scratch");
-        take.commit();
-        if (s.query_scratch) s.mem.free(s.query_scratch, (size_t)s.query_bytes);  // (no query is in flight: the host form is blocking)
-        s.query_scratch = fresh;
-        s.query_bytes = want;
-        s.query_capacity = n;
-    }
+    grow_scratch(s, s.query_scratch, s.query_bytes, (uint64_t)n * kQueryRayBytes, "ray query", "the scratch of this batch brings", "query scratch");
     char *base = (char *)s.query_scratch;
     uint32_t *out = (uint32_t *)(base + n * kQueryInBytes);  // word offsets per ray: kind 0, t 1, normal 2, position 5, primitive 8, direction 9
     if (q.mode == 2u) Q.pixels = (const uint2 *)base;

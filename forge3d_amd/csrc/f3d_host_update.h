@@ -1,6 +1,8 @@
 // f3d_host_update.h -- part of f3d_host.hip (included there once, after the session's enqueue helpers): the updates of a live
 // session -- re-arm (sun / seed / exposure / IBL intensity / frame budget), re-aim (+ camera), re-mesh (+ a moved or another
 // mesh), re-terrain (+ new DEM samples) -- and their C ABI: what they share in Update, what is an update's own in its function.
+// Behind them what every later entry of a live session uses too (queries, rasters, drape): check_budget, grow_scratch,
+// check_flags, check_no_wait, update_entry.
 #pragma once
 
 namespace {
@@ -119,6 +121,37 @@ void check_budget(const f3d_session &s, uint64_t planned, const char *update, co
     if (planned > s.budget)
         fail(F3D_STATUS_RENDER, "%s exceeds the memory budget: %s the tracked total to %llu > limit %llu", update, brings,
              (unsigned long long)planned, (unsigned long long)s.budget);
+}
+
+// A scratch of the session that only grows (the query's, the rasters'): for a call that wants more than it holds, the larger
+// buffer is taken and committed, then the old one goes back -- nothing is in flight on it, the host forms are blocking.
+void grow_scratch(f3d_session &s, void *&scratch, uint64_t &bytes, uint64_t want, const char *noun, const char *brings, const char *what) {
+    if (want <= bytes) return;
+    check_budget(s, s.mem.device_bytes - bytes + want, noun, brings);
+    Ledger::Take take{s.mem};
+    void *fresh = take((size_t)want, what);
+    take.commit();
+    if (scratch) s.mem.free(scratch, (size_t)bytes);
+    scratch = fresh;
+    bytes = want;
+}
+
+// The flags every entry with a host and a device form shares, under the values of all their families (f3d_terrain_pt.h).
+constexpr uint32_t kDevicePointers = 4u, kNoWait = 8u;
+static_assert(F3D_QUERY_DEVICE_POINTERS == kDevicePointers && F3D_RASTER_DEVICE_POINTERS == kDevicePointers && F3D_HORIZON_DEVICE_POINTERS == kDevicePointers &&
+              F3D_IRRADIATION_DEVICE_POINTERS == kDevicePointers && F3D_CLEARANCE_DEVICE_POINTERS == kDevicePointers && F3D_DRAPE_DEVICE_POINTERS == kDevicePointers &&
+              F3D_QUERY_NO_WAIT == kNoWait && F3D_RASTER_NO_WAIT == kNoWait && F3D_HORIZON_NO_WAIT == kNoWait && F3D_IRRADIATION_NO_WAIT == kNoWait &&
+              F3D_CLEARANCE_NO_WAIT == kNoWait && F3D_DRAPE_NO_WAIT == kNoWait, "one DEVICE_POINTERS and one NO_WAIT for every family");
+
+void check_flags(uint32_t flags, uint32_t known, const char *noun, const char *names) {
+    if (flags & ~known) fail(F3D_STATUS_VALUE, "unknown %s flags 0x%x (%s)", noun, flags, names);
+}
+
+// Returns whether the call is in the device form; `why`: what the host form promises at its return.
+bool check_no_wait(uint32_t flags, const char *why = "results in host memory are there") {
+    const bool device_form = (flags & kDevicePointers) != 0u;
+    if ((flags & kNoWait) && !device_form) fail(F3D_STATUS_VALUE, "NO_WAIT needs DEVICE_POINTERS: %s when the call returns", why);
+    return device_form;
 }
 
 void rearm(f3d_session &s, const f3d_session_rearm_desc &r) {

@@ -17,6 +17,56 @@ RESERVOIR_BYTES = 16
 WELFORD_WINDOW = 32
 
 
+# What the raster and query methods share in front of the library.  An input is a NumPy array (the host form) or a torch
+# tensor (the device form); a method decides the form ONCE (_form) and hands the device down -- None is the host form -- and
+# every output comes back in the input's form.
+def _is_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+_torch = None  # the torch module and, per NumPy dtype of an output, the tensor dtype with its bits: set when the first tensor comes in
+_TENSOR_BITS = {}
+
+
+def _form(x, wait, noun, plural, device=None):
+    """The form of a call whose input is ``x``: the device the outputs go to for a tensor (or ``device``, for a call without
+    an input), None for the host form -- with the two refusals of a form, raised before anything is converted or allocated."""
+    global _torch
+    if device is None and (x is None or isinstance(x, np.ndarray) or type(x).__module__.split(".")[0] != "torch"):
+        if not wait:
+            raise ValueError(f"wait=False is for tensor {plural}: results in host memory are there when the call returns")
+        return None
+    if x is not None and not x.is_cuda:
+        raise ValueError(f"a tensor {noun} needs a tensor on the session's device (NumPy arrays take the host form)")
+    if _torch is None:
+        import torch  # (only for callers who hand tensors in)
+
+        _TENSOR_BITS.update({np.float32: torch.float32, np.uint32: torch.int32, np.uint64: torch.int64})
+        _torch = torch
+    return x.device if device is None else device
+
+
+def _rows4(rows, device):
+    """(K, 3) or (K, 4) rows as contiguous float32 (K, 4), the missing column 0; a tensor (``device`` not None) stays one."""
+    if device is not None:
+        t = rows.to(_torch.float32)
+    else:
+        t = np.asarray(rows, dtype=np.float32)
+    if t.ndim != 2 or t.shape[1] not in (3, 4):
+        raise ValueError(f"expected shape (K, 4) or (K, 3), got {tuple(t.shape)}")
+    if device is not None:
+        return (_torch.cat([t, _torch.zeros_like(t[:, :1])], 1) if t.shape[1] == 3 else t).contiguous()
+    return np.ascontiguousarray(np.concatenate([t, np.zeros((t.shape[0], 1), np.float32)], 1) if t.shape[1] == 3 else t)
+
+
+def _output(device, want, shape, dtype):
+    """An output of ``shape`` and NumPy ``dtype``, None unless ``want``: NumPy zeros for the host form, an uninitialised tensor
+    on ``device`` for the device form (the kernel writes every element; uint32 is int32 bits, uint64 int64 bits)."""
+    if not want:
+        return None
+    return np.zeros(shape, dtype) if device is None else _torch.empty(shape, dtype=_TENSOR_BITS[dtype], device=device)
+
+
 class TerrainSession:
     def __init__(self, heightmap, width, height, camera=None, *, row_begin=0, row_end=0, device=-1, stream=0,
                  memory_budget_bytes=0, kernel_variant=0, ext_reservoirs=(None, None), ext_stats=None, bands=0,
@@ -369,56 +419,65 @@ class TerrainSession:
         self._check(self._lib.f3d_session_render(self._handle, C.byref(o), self._err, len(self._err)))
         return _native.result_dict(rgba, alb, nrm, dep, o, self._armed["sun_azimuth_deg"], self._armed["sun_elevation_deg"])
 
+    # -- what the query and the four raster families share -----------------------------------
+    def _region(self, region):
+        """``(row0, col0, rows, cols)``, default the whole DEM.  Whether it lies inside the DEM is the library's check."""
+        dem_h, dem_w = self.dem_shape
+        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
+        if min(row0, col0, rows, cols) < 0:
+            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        return row0, col0, rows, cols
+
+    def _call(self, entry, q, device, wait, region, member, source, outputs):
+        """One call of ``entry`` with the descriptor ``q``, whose own members the caller has set: here its size, the flags of
+        the form _form() decided (``device``; the same values in every family), the region, the input ``source`` under
+        ``member`` and the ``outputs`` (pairs of member name and array or None).  ``source`` is alive until the call returns."""
+        q.struct_size = C.sizeof(q)
+        if region is not None:
+            q.row0, q.col0, q.rows, q.cols = region
+        if device is not None:
+            q.flags |= _native.RASTER_DEVICE_POINTERS | (0 if wait else _native.RASTER_NO_WAIT)
+            if source is not None and source.shape[0]:
+                setattr(q, member, source.data_ptr())
+            for name, a in outputs:
+                if a is not None:
+                    setattr(q, name, a.data_ptr())
+        else:
+            if source is not None and source.shape[0]:
+                setattr(q, member, source.ctypes.data)
+            for name, a in outputs:
+                if a is not None:
+                    setattr(q, name, a.ctypes.data)
+        self._check(entry(self._handle, C.byref(q), self._err, len(self._err)))
+
     # -- ray queries: pick, line of sight, ground -----------------------------------------
     GROUND_CLEARANCE = 10.0  # ground() starts its rays this far above the scene's top
+
+    _QUERY_OUTPUTS = {"kind": ((), np.uint32), "t": ((), np.float32), "normal": ((3,), np.float32), "position": ((3,), np.float32),
+                      "primitive": ((), np.uint32), "direction": ((3,), np.float32)}  # per ray: shape and dtype of each output member
 
     def _query(self, mode: int, flags: int, rays, width: int, dtype, outputs, wait: bool = True) -> dict:
         """One f3d_session_query.  ``rays``: a NumPy array (host form: blocking, staged copies through the session's scratch) or
         a torch tensor on the session's device (DEVICE_POINTERS: nothing copied, results are tensors; ``wait=False`` returns
         with the kernel in flight on the session's stream).  ``outputs``: names of f3d_session_query_desc's output members."""
-        shapes = {"kind": ((), np.uint32), "t": ((), np.float32), "normal": ((3,), np.float32), "position": ((3,), np.float32),
-                  "primitive": ((), np.uint32), "direction": ((3,), np.float32)}
-        q = _native.QueryDesc()
-        q.struct_size = C.sizeof(_native.QueryDesc)
-        q.mode = int(mode)
-        out = {}
-        if type(rays).__module__.split(".")[0] == "torch":
-            import torch  # (only for callers who hand tensors in)
-
-            if not rays.is_cuda:
-                raise ValueError("a tensor query needs a tensor on the session's device (NumPy arrays take the host form)")
-            want = torch.float32 if dtype == np.float32 else torch.int32
-            if dtype != np.float32 and rays.dtype not in (torch.int32, torch.int64, torch.uint8, torch.int16):
+        device = _form(rays, wait, "query", "queries")
+        if device is not None:
+            if dtype != np.float32 and rays.dtype not in (_torch.int32, _torch.int64, _torch.uint8, _torch.int16):
                 raise ValueError("pixels must be an integer tensor")
             if dtype != np.float32 and bool(((rays < 0) | (rays > 0x7FFFFFFF)).any()):
                 raise ValueError("pixel coordinates must not be negative")
-            r = rays.to(want).contiguous()
-            if r.ndim != 2 or r.shape[1] != width:
-                raise ValueError(f"expected shape (N, {width}), got {tuple(rays.shape)}")
-            n = int(r.shape[0])
-            tdt = {np.uint32: torch.int32, np.float32: torch.float32}
-            for name in outputs:
-                tail, dt = shapes[name]
-                out[name] = torch.empty((n, *tail), dtype=tdt[dt], device=r.device)
-                setattr(q, name, out[name].data_ptr() if n else None)
-            q.flags = int(flags) | _native.QUERY_DEVICE_POINTERS | (0 if wait else _native.QUERY_NO_WAIT)
-            q.count, q.rays = n, (r.data_ptr() if n else None)
+            r = rays.to(_torch.float32 if dtype == np.float32 else _torch.int32).contiguous()
         else:
             r = np.ascontiguousarray(rays, dtype=dtype)
             if dtype != np.float32 and np.asarray(rays).size and (np.asarray(rays).min() < 0):
                 raise ValueError("pixel coordinates must not be negative")
-            if r.ndim != 2 or r.shape[1] != width:
-                raise ValueError(f"expected shape (N, {width}), got {np.asarray(rays).shape}")
-            if not wait:
-                raise ValueError("wait=False is for tensor queries: results in host memory are there when the call returns")
-            n = int(r.shape[0])
-            for name in outputs:
-                tail, dt = shapes[name]
-                out[name] = np.zeros((n, *tail), dt)
-                setattr(q, name, out[name].ctypes.data if n else None)
-            q.flags = int(flags)
-            q.count, q.rays = n, (r.ctypes.data if n else None)
-        self._check(self._lib.f3d_session_query(self._handle, C.byref(q), self._err, len(self._err)))
+        if r.ndim != 2 or r.shape[1] != width:
+            raise ValueError(f"expected shape (N, {width}), got {tuple(np.shape(rays))}")
+        n = int(r.shape[0])
+        q = _native.QueryDesc()
+        q.mode, q.flags, q.count = int(mode), int(flags), n
+        out = {name: _output(device, True, (n, *self._QUERY_OUTPUTS[name][0]), self._QUERY_OUTPUTS[name][1]) for name in outputs}
+        self._call(self._lib.f3d_session_query, q, device, wait, None, "rays", r, out.items())
         return out
 
     def trace(self, rays, *, terrain_only: bool = False, wait: bool = True) -> dict:
@@ -455,7 +514,7 @@ class TerrainSession:
             scene_top = self._terrain_top if (terrain_only or self._mesh_top is None) else max(self._terrain_top, self._mesh_top)
             top = scene_top + self.GROUND_CLEARANCE
         top = float(np.float32(top))
-        if type(xz).__module__.split(".")[0] == "torch":
+        if _is_tensor(xz):
             import torch
 
             p = xz.to(torch.float32)
@@ -491,61 +550,30 @@ class TerrainSession:
         number of targets seen for ``count`` (int32 bits as a tensor), ``(masks, count)`` for both."""
         if not (masks or count):
             raise ValueError("visibility() needs an output: masks, count or both")
-        dem_h, dem_w = self.dem_shape
-        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
-        if min(row0, col0, rows, cols) < 0:
-            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
-        q = _native.RasterDesc()
-        q.struct_size = C.sizeof(_native.RasterDesc)
-        q.mode = _native.RASTER_TOWARD_POINT if toward else _native.RASTER_ALONG_DIRECTION
-        q.flags = (_native.RASTER_CURVED if curved else 0) | (_native.RASTER_TERRAIN_ONLY if terrain_only else 0)
-        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
-        q.lift = float(lift)
+        region = self._region(region)
+        rows, cols = region[2:]
         n = rows * cols
         words = (n + 63) // 64
-        tensors = type(targets).__module__.split(".")[0] == "torch"
-        if tensors:
-            import torch  # (only for callers who hand tensors in)
-
-            if not targets.is_cuda:
-                raise ValueError("a tensor raster needs a tensor on the session's device (NumPy arrays take the host form)")
-            t = targets.to(torch.float32)
-            if t.ndim != 2 or t.shape[1] not in (3, 4):
-                raise ValueError(f"expected shape (K, 4) or (K, 3), got {tuple(targets.shape)}")
-            if t.shape[1] == 3:
-                t = torch.cat([t, torch.zeros_like(t[:, :1])], 1)
-            t = t.contiguous()
-            k = int(t.shape[0])
-            q.flags |= _native.RASTER_DEVICE_POINTERS | (0 if wait else _native.RASTER_NO_WAIT)
-            q.target_count, q.targets = k, (t.data_ptr() if k else None)
-            # (the kernel writes every word of both; without targets nothing runs and nothing is seen)
-            m_out = torch.empty((k, words), dtype=torch.int64, device=t.device) if masks else None
-            c_out = (torch.empty if k else torch.zeros)(n, dtype=torch.int32, device=t.device) if count else None
-            q.masks, q.count = (m_out.data_ptr() if masks else None), (c_out.data_ptr() if count else None)
+        q = _native.RasterDesc()
+        q.mode = _native.RASTER_TOWARD_POINT if toward else _native.RASTER_ALONG_DIRECTION
+        q.flags = (_native.RASTER_CURVED if curved else 0) | (_native.RASTER_TERRAIN_ONLY if terrain_only else 0)
+        q.lift = float(lift)
+        device = _form(targets, wait, "raster", "rasters")
+        if targets is None:
+            if toward:
+                raise ValueError("targets=None is the session's sun direction: it needs toward=False")
+            q.flags |= _native.RASTER_SESSION_SUN
+            t, k = None, 1
         else:
-            if not wait:
-                raise ValueError("wait=False is for tensor rasters: results in host memory are there when the call returns")
-            if targets is None:
-                if toward:
-                    raise ValueError("targets=None is the session's sun direction: it needs toward=False")
-                q.flags |= _native.RASTER_SESSION_SUN
-                k = 1
-            else:
-                t = np.asarray(targets, dtype=np.float32)
-                if t.ndim != 2 or t.shape[1] not in (3, 4):
-                    raise ValueError(f"expected shape (K, 4) or (K, 3), got {t.shape}")
-                if t.shape[1] == 3:
-                    t = np.concatenate([t, np.zeros((t.shape[0], 1), np.float32)], 1)
-                t = np.ascontiguousarray(t)
-                k = int(t.shape[0])
-                q.target_count, q.targets = k, (t.ctypes.data if k else None)
-            m_out = np.zeros((k, words), np.uint64) if masks else None
-            c_out = np.zeros(n, np.uint32) if count else None
-            q.masks, q.count = (m_out.ctypes.data if masks else None), (c_out.ctypes.data if count else None)
-        self._check(self._lib.f3d_session_raster(self._handle, C.byref(q), self._err, len(self._err)))  # (t lives until here)
+            t = _rows4(targets, device)
+            k = q.target_count = int(t.shape[0])
+        m_out, c_out = _output(device, masks, (k, words), np.uint64), _output(device, count, (n,), np.uint32)
+        if device is not None and count and not k:  # (the kernel writes every word of both; without targets nothing runs and nothing is seen)
+            c_out.zero_()
+        self._call(self._lib.f3d_session_raster, q, device, wait, region, "targets", t, (("masks", m_out), ("count", c_out)))
         out = []
-        if masks and tensors:
-            bit = torch.arange(64, dtype=torch.int64, device=m_out.device)
+        if masks and device is not None:
+            bit = _torch.arange(64, dtype=_torch.int64, device=device)
             out.append((((m_out.unsqueeze(-1) >> bit) & 1) != 0).reshape(k, words * 64)[:, :n].reshape(k, rows, cols))
         elif masks:
             bits = np.unpackbits(m_out.view(np.uint8).reshape(k, words * 8), axis=1, bitorder="little")
@@ -554,14 +582,9 @@ class TerrainSession:
             out.append(c_out.reshape(rows, cols))
         return out[0] if len(out) == 1 else tuple(out)
 
-    def viewshed(self, observer, *, observer_height: float = 1.7, target_height: float = 0.0, max_distance=None,
-                 curved: bool = False, terrain_only: bool = False, region=None):
-        """Which DEM samples (raised by ``target_height``) does an observer see?  ``observer``: ``(x, y, z)``, an absolute
-        position, or ``(x, z)``, standing ``observer_height`` above ground(); an (M, 3) / (M, 2) array of observers gives
-        the cumulative viewshed.  ``max_distance``: samples farther away horizontally are not visible.  ``curved``: the
-        sight lines follow the session's earth curvature and refraction (one effective radius for the whole DEM).
-        Returns the bool array (rows, cols), True: visible, for one observer; for several the uint32 array of how many
-        observers see each sample.  An observer outside the DEM's footprint given as ``(x, z)`` sees nothing."""
+    def _observers(self, observer, observer_height, max_distance):
+        """viewshed()'s observer forms as the float32 (M, 4) rows ``(x, y, z, max_distance or 0)`` of a raster call, and whether
+        ONE observer was given: ``(x, z)`` stands ``observer_height`` above ground(), and is dropped without ground under it."""
         obs = np.asarray(observer, dtype=np.float32)
         single = obs.ndim == 1
         obs = np.atleast_2d(obs)
@@ -574,7 +597,17 @@ class TerrainSession:
         w = np.float32(0.0 if max_distance is None else max_distance)
         if max_distance is not None and not w > 0.0:
             raise ValueError(f"max_distance must be positive, got {max_distance}")
-        targets = np.concatenate([obs, np.full((len(obs), 1), w, np.float32)], 1).astype(np.float32)
+        return np.concatenate([obs, np.full((len(obs), 1), w, np.float32)], 1).astype(np.float32), single
+
+    def viewshed(self, observer, *, observer_height: float = 1.7, target_height: float = 0.0, max_distance=None,
+                 curved: bool = False, terrain_only: bool = False, region=None):
+        """Which DEM samples (raised by ``target_height``) does an observer see?  ``observer``: ``(x, y, z)``, an absolute
+        position, or ``(x, z)``, standing ``observer_height`` above ground(); an (M, 3) / (M, 2) array of observers gives
+        the cumulative viewshed.  ``max_distance``: samples farther away horizontally are not visible.  ``curved``: the
+        sight lines follow the session's earth curvature and refraction (one effective radius for the whole DEM).
+        Returns the bool array (rows, cols), True: visible, for one observer; for several the uint32 array of how many
+        observers see each sample.  An observer outside the DEM's footprint given as ``(x, z)`` sees nothing."""
+        targets, single = self._observers(observer, observer_height, max_distance)
         lift = np.float32(np.float32(target_height) + np.float32(self.SURFACE_BIAS))
         if single:
             if len(targets) == 0:  # (no target is a checked no-op of the library: the region is validated, nothing is seen)
@@ -614,7 +647,7 @@ class TerrainSession:
                 raise ValueError(f"azimuths must be 1 to {_native.HORIZON_MAX_AZIMUTHS}, got {n}")
             a = np.radians(360.0 * np.arange(n, dtype=np.float64) / n)
             return np.stack([np.sin(a), -np.cos(a)], 1).astype(np.float32)
-        if type(azimuths).__module__.split(".")[0] == "torch":
+        if _is_tensor(azimuths):
             import torch
 
             d = azimuths.to(torch.float32)
@@ -627,37 +660,17 @@ class TerrainSession:
         return d
 
     def _horizon(self, azimuths, lift, curved, region, planes, sky_view, wait):
-        dem_h, dem_w = self.dem_shape
-        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
-        if min(row0, col0, rows, cols) < 0:
-            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        region = self._region(region)
+        rows, cols = region[2:]
         d = self.horizon_directions(azimuths)
-        k, n = int(d.shape[0]), rows * cols
+        k = int(d.shape[0])
         q = _native.HorizonDesc()
-        q.struct_size = C.sizeof(_native.HorizonDesc)
         q.flags = _native.HORIZON_CURVED if curved else 0
-        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.lift = float(lift)
         q.azimuth_count = k
-        tensors = not isinstance(d, np.ndarray)
-        if tensors:
-            import torch
-
-            if not d.is_cuda:
-                raise ValueError("a tensor horizon needs a tensor on the session's device (NumPy arrays take the host form)")
-            q.flags |= _native.HORIZON_DEVICE_POINTERS | (0 if wait else _native.HORIZON_NO_WAIT)
-            h_out = torch.empty((k, rows, cols), dtype=torch.float32, device=d.device) if planes else None
-            s_out = torch.empty((rows, cols), dtype=torch.float32, device=d.device) if sky_view else None
-            q.azimuths = d.data_ptr() if k else None
-            q.horizon, q.sky_view = (h_out.data_ptr() if planes else None), (s_out.data_ptr() if sky_view else None)
-        else:
-            if not wait:
-                raise ValueError("wait=False is for tensor horizons: results in host memory are there when the call returns")
-            h_out = np.zeros((k, rows, cols), np.float32) if planes else None
-            s_out = np.zeros((rows, cols), np.float32) if sky_view else None
-            q.azimuths = d.ctypes.data if k else None
-            q.horizon, q.sky_view = (h_out.ctypes.data if planes else None), (s_out.ctypes.data if sky_view else None)
-        self._check(self._lib.f3d_session_horizon(self._handle, C.byref(q), self._err, len(self._err)))  # (d lives until here)
+        device = _form(d, wait, "horizon", "horizons")
+        h_out, s_out = _output(device, planes, (k, rows, cols), np.float32), _output(device, sky_view, (rows, cols), np.float32)
+        self._call(self._lib.f3d_session_horizon, q, device, wait, region, "azimuths", d, (("horizon", h_out), ("sky_view", s_out)))
         return h_out, s_out
 
     def horizon(self, azimuths=16, *, lift: float = SURFACE_BIAS, curved: bool = False, region=None, sky_view: bool = False,
@@ -696,46 +709,16 @@ class TerrainSession:
         around the threshold."""
         if not (planes or lowest):
             raise ValueError("clearance() needs an output: planes, lowest or both")
-        dem_h, dem_w = self.dem_shape
-        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
-        if min(row0, col0, rows, cols) < 0:
-            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        region = self._region(region)
+        rows, cols = region[2:]
+        device = _form(observers, wait, "clearance", "clearances")
+        t = _rows4(observers, device)
+        k = int(t.shape[0])
         q = _native.ClearanceDesc()
-        q.struct_size = C.sizeof(_native.ClearanceDesc)
         q.flags = _native.CLEARANCE_CURVED if curved else 0
-        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
-        if type(observers).__module__.split(".")[0] == "torch":
-            import torch  # (only for callers who hand tensors in)
-
-            if not observers.is_cuda:
-                raise ValueError("a tensor clearance needs a tensor on the session's device (NumPy arrays take the host form)")
-            t = observers.to(torch.float32)
-            if t.ndim != 2 or t.shape[1] not in (3, 4):
-                raise ValueError(f"expected shape (K, 4) or (K, 3), got {tuple(observers.shape)}")
-            if t.shape[1] == 3:
-                t = torch.cat([t, torch.zeros_like(t[:, :1])], 1)
-            t = t.contiguous()
-            k = int(t.shape[0])
-            q.flags |= _native.CLEARANCE_DEVICE_POINTERS | (0 if wait else _native.CLEARANCE_NO_WAIT)
-            h_out = torch.empty((k, rows, cols), dtype=torch.float32, device=t.device) if planes else None
-            l_out = torch.empty((rows, cols), dtype=torch.float32, device=t.device) if lowest else None
-            q.observer_count, q.observers = k, (t.data_ptr() if k else None)
-            q.height, q.lowest = (h_out.data_ptr() if planes else None), (l_out.data_ptr() if lowest else None)
-        else:
-            if not wait:
-                raise ValueError("wait=False is for tensor clearances: results in host memory are there when the call returns")
-            t = np.asarray(observers, dtype=np.float32)
-            if t.ndim != 2 or t.shape[1] not in (3, 4):
-                raise ValueError(f"expected shape (K, 4) or (K, 3), got {t.shape}")
-            if t.shape[1] == 3:
-                t = np.concatenate([t, np.zeros((t.shape[0], 1), np.float32)], 1)
-            t = np.ascontiguousarray(t)
-            k = int(t.shape[0])
-            h_out = np.zeros((k, rows, cols), np.float32) if planes else None
-            l_out = np.zeros((rows, cols), np.float32) if lowest else None
-            q.observer_count, q.observers = k, (t.ctypes.data if k else None)
-            q.height, q.lowest = (h_out.ctypes.data if planes else None), (l_out.ctypes.data if lowest else None)
-        self._check(self._lib.f3d_session_clearance(self._handle, C.byref(q), self._err, len(self._err)))  # (t lives until here)
+        q.observer_count = k
+        h_out, l_out = _output(device, planes, (k, rows, cols), np.float32), _output(device, lowest, (rows, cols), np.float32)
+        self._call(self._lib.f3d_session_clearance, q, device, wait, region, "observers", t, (("height", h_out), ("lowest", l_out)))
         return (h_out, l_out) if (planes and lowest) else (h_out if planes else l_out)
 
     def visible_height(self, observer, *, observer_height: float = 1.7, max_distance=None, curved: bool = False, region=None):
@@ -747,24 +730,13 @@ class TerrainSession:
         range or no observer has ground under it (then every sample is +inf, as viewshed() sees nothing).
         ``viewshed(obs, target_height=th) == (visible_height(obs) < th + SURFACE_BIAS)`` away from a band of rounding around
         the threshold (terrain only: a mesh hides nothing here)."""
-        obs = np.asarray(observer, dtype=np.float32)
-        obs = np.atleast_2d(obs)
-        if obs.ndim != 2 or obs.shape[1] not in (2, 3):
-            raise ValueError(f"observer must be (x, y, z), (x, z) or an array of them, got shape {np.asarray(observer).shape}")
-        if obs.shape[1] == 2:
-            y = self.ground(obs) + np.float32(observer_height)  # (the terrain: an observer does not stand on the mesh)
-            obs = np.stack([obs[:, 0], y.astype(np.float32), obs[:, 1]], 1)
-            obs = obs[np.isfinite(obs).all(1)]  # (no ground under it: nothing to stand on, nothing seen)
-        w = np.float32(0.0 if max_distance is None else max_distance)
-        if max_distance is not None and not w > 0.0:
-            raise ValueError(f"max_distance must be positive, got {max_distance}")
-        if len(obs) == 0:
+        observers, _ = self._observers(observer, observer_height, max_distance)
+        if len(observers) == 0:
             dem_h, dem_w = self.dem_shape
             row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
             if min(row0, col0) < 0 or min(rows, cols) <= 0 or row0 + rows > dem_h or col0 + cols > dem_w:
                 raise ValueError(f"region=(row0, col0, rows, cols)={tuple(region)} is empty or reaches outside the {dem_h}x{dem_w} DEM")
             return np.full((rows, cols), np.inf, np.float32)
-        observers = np.concatenate([obs, np.full((len(obs), 1), w, np.float32)], 1).astype(np.float32)
         return self.clearance(observers, curved=curved, region=region, planes=False, lowest=True)
 
     # -- irradiation rasters: beam energy over a sun track, surface normals --------------------
@@ -773,7 +745,7 @@ class TerrainSession:
         """The (K, 4) float32 rows ``(x, y, z, weight)`` an irradiation() call with these arguments sends: ``directions`` (K, 3)
         with ``weights`` (K,), or (K, 4) with the weight in the last column (``weights`` must then be None); a direction with
         ``y <= 0`` -- the sun below the horizontal -- gets weight 0.  A torch tensor stays a tensor."""
-        tensors = type(directions).__module__.split(".")[0] == "torch"
+        tensors = _is_tensor(directions)
         if tensors:
             import torch
 
@@ -803,40 +775,17 @@ class TerrainSession:
         return np.ascontiguousarray(np.concatenate([xyz, w[:, None]], 1), dtype=np.float32)
 
     def _irradiation(self, terms, flags, lift, region, energy, count, normal, wait, device=None):
-        dem_h, dem_w = self.dem_shape
-        row0, col0, rows, cols = (0, 0, dem_h, dem_w) if region is None else (int(v) for v in region)
-        if min(row0, col0, rows, cols) < 0:
-            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        region = self._region(region)
+        rows, cols = region[2:]
         q = _native.IrradiationDesc()
-        q.struct_size = C.sizeof(_native.IrradiationDesc)
         q.flags = flags
-        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.lift = float(lift)
-        k = 0 if terms is None else int(terms.shape[0])
-        q.direction_count = k
-        tensors = device is not None or (terms is not None and not isinstance(terms, np.ndarray))
-        if tensors:
-            import torch
-
-            if terms is not None and not terms.is_cuda:
-                raise ValueError("a tensor irradiation needs a tensor on the session's device (NumPy arrays take the host form)")
-            q.flags |= _native.IRRADIATION_DEVICE_POINTERS | (0 if wait else _native.IRRADIATION_NO_WAIT)
-            make = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=device if terms is None else terms.device)
-            e_out = make((rows, cols), torch.float32) if energy else None
-            c_out = make((rows, cols), torch.int32) if count else None
-            n_out = make((rows, cols, 3), torch.float32) if normal else None
-            q.directions = terms.data_ptr() if k else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-        else:
-            if not wait:
-                raise ValueError("wait=False is for tensor irradiations: results in host memory are there when the call returns")
-            e_out = np.zeros((rows, cols), np.float32) if energy else None
-            c_out = np.zeros((rows, cols), np.uint32) if count else None
-            n_out = np.zeros((rows, cols, 3), np.float32) if normal else None
-            q.directions = terms.ctypes.data if k else None
-            ptr = lambda a: None if a is None else a.ctypes.data
-        q.energy, q.count, q.normal = ptr(e_out), ptr(c_out), ptr(n_out)
-        self._check(self._lib.f3d_session_irradiation(self._handle, C.byref(q), self._err, len(self._err)))  # (terms lives until here)
+        q.direction_count = 0 if terms is None else int(terms.shape[0])
+        device = _form(terms, wait, "irradiation", "irradiations", device)
+        e_out, c_out = _output(device, energy, (rows, cols), np.float32), _output(device, count, (rows, cols), np.uint32)
+        n_out = _output(device, normal, (rows, cols, 3), np.float32)
+        self._call(self._lib.f3d_session_irradiation, q, device, wait, region, "directions", terms,
+                   (("energy", e_out), ("count", c_out), ("normal", n_out)))
         return e_out, c_out, n_out
 
     def irradiation(self, directions, weights=None, *, horizontal: bool = False, curved: bool = True, terrain_only: bool = False,
