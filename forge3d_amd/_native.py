@@ -218,6 +218,19 @@ class ClearanceDesc(C.Structure):
 CLEARANCE_CURVED, CLEARANCE_DEVICE_POINTERS, CLEARANCE_NO_WAIT = 2, 4, 8
 
 
+class UmbraDesc(C.Structure):
+    """f3d_session_umbra_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("direction_count", C.c_uint32), ("reserved", C.c_uint32),
+        ("directions", C.c_void_p), ("depth", C.c_void_p), ("deepest", C.c_void_p),
+    ]
+
+
+UMBRA_CURVED, UMBRA_DEVICE_POINTERS, UMBRA_NO_WAIT, UMBRA_SESSION_SUN = 2, 4, 8, 16
+
+
 class DrapeDesc(C.Structure):
     """f3d_session_drape_desc"""
     _fields_ = [
@@ -279,6 +292,7 @@ ABI = [
     ("f3d_session_horizon", C.c_int, [C.c_void_p, _P(HorizonDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_irradiation", C.c_int, [C.c_void_p, _P(IrradiationDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_clearance", C.c_int, [C.c_void_p, _P(ClearanceDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_umbra", C.c_int, [C.c_void_p, _P(UmbraDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape", C.c_int, [C.c_void_p, _P(DrapeDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),

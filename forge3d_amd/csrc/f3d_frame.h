@@ -17,6 +17,7 @@
 #include "f3d_horizon.h"
 #include "f3d_irradiation.h"
 #include "f3d_clearance.h"
+#include "f3d_umbra.h"
 #include "f3d_lds.h"
 #include "f3d_tiles.h"
 #include "f3d_skyblocks.h"
@@ -955,6 +956,31 @@ __global__ __launch_bounds__(kWave) void k_clearance(const ClearanceParams R) {
         lowest = f_min(lowest, L);  // (a NaN plane is ignored)
     }
     if (R.lowest) R.lowest[n] = lowest;
+}
+
+// Shadow-depth rasters on a live session (f3d_session_umbra; f3d_umbra.h): k_clearance's shape -- one wave a workgroup, one
+// lane a DEM sample of the region (64 consecutive samples, or with R.block an 8 x 8 block: measured, profiles/README.md), the
+// band table's per-level layout in 128 bytes of LDS.  The loop over the directions is wave-uniform and every lane reads the
+// direction at the same address (none: the session's sun, one direction); the lane keeps its sample and the maximum over the
+// directions in registers and writes what it owns with ordinary stores.  With depth null nothing of size direction_count x
+// rows * cols exists anywhere.
+__global__ __launch_bounds__(kWave) void k_umbra(const UmbraParams R) {
+    __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
+    load_level_table(table, R.terrain);
+    const HorizonLevels levels{table};
+    const uint32_t total = R.rows * R.cols;
+    uint32_t n;
+    if (!lane_sample(R.rows, R.cols, R.block, n)) return;  // (no wave primitive below)
+    uint32_t i, j;
+    const V3 g = umbra_sample(R, n, i, j);
+    float deepest = 0.0f;
+    for (uint32_t k = 0u; k < R.direction_count; k++) {
+        const float4 direction = R.directions ? R.directions[k] : float4{R.sun.x, R.sun.y, R.sun.z, 0.0f};
+        const float L = umbra_depth(R, g, i, j, direction, levels);
+        if (R.depth) R.depth[(size_t)k * total + n] = L;
+        deepest = f_max(deepest, L);  // (a NaN plane is ignored)
+    }
+    if (R.deepest) R.deepest[n] = deepest;
 }
 
 // Irradiation rasters on a live session (f3d_session_irradiation; f3d_irradiation.h): k_raster's shape -- one wave a

@@ -131,7 +131,7 @@ struct f3d_session {
     // ray queries (f3d_session_query, host form): the scratch rays and results pass through, grown only for a larger batch
     void *query_scratch = nullptr;
     uint64_t query_bytes = 0;
-    // the four raster families (f3d_host_rasters.h, host form): input and outputs pass through, grown only for a larger call
+    // the five raster families (f3d_host_rasters.h, host form): input and outputs pass through, grown only for a larger call
     void *raster_scratch = nullptr;
     uint64_t raster_bytes = 0;
     // drape (f3d_session_drape): the buffer params.drape names -- a 64-byte DrapeDev record, then rows x cols binary16 RGBA
@@ -1001,7 +1001,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 #include "f3d_host_halo.h"  // peer halos: the pull kernel, the batch enqueue and their C ABI
 #include "f3d_host_update.h"  // session updates (re-arm, re-aim, re-mesh, re-terrain): one path, their own steps and their C ABI
 #include "f3d_host_query.h"  // ray queries on a live session: checks, scratch, staged copies, launch and their C ABI
-#include "f3d_host_rasters.h"  // visibility, horizon, irradiation and clearance rasters on a live session: one path, their own steps and their C ABI
+#include "f3d_host_rasters.h"  // visibility, horizon, irradiation, clearance and shadow-depth rasters on a live session: one path, their own steps and their C ABI
 #include "f3d_host_drape.h"  // an image draped over the terrain of a live session: checks, buffer, staged upload, packing and its C ABI
 
 // ---------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// f3d_host_rasters.h -- part of f3d_host.hip (included there once, after the ray queries): the four raster families of a live
+// f3d_host_rasters.h -- part of f3d_host.hip (included there once, after the ray queries): the five raster families of a live
 // session -- visibility (f3d_session_raster; the kernel's lane is f3d_raster.h), horizon (f3d_session_horizon; f3d_horizon.h),
-// irradiation (f3d_session_irradiation; f3d_irradiation.h), clearance (f3d_session_clearance; f3d_clearance.h) -- and their C
+// irradiation (f3d_session_irradiation; f3d_irradiation.h), clearance (f3d_session_clearance; f3d_clearance.h), shadow depth
+// (f3d_session_umbra; f3d_umbra.h) -- and their C
 // ABI: what they share in raster_front (raster_flags) / raster_region / raster_run, what is a family's own in its function.  A family is:
 // the shared front checks, its own checks (the order in which refusals win is contract), its *Params, the list of its
 // segments, raster_run.
@@ -9,6 +10,7 @@
 #include "f3d_clearance.h"
 #include "f3d_horizon.h"
 #include "f3d_raster_scratch.h"
+#include "f3d_umbra.h"
 
 namespace {
 
@@ -54,7 +56,7 @@ RasterSegment raster_input(const void *caller, uint64_t bytes, const T *&member)
 }
 
 // The call itself, behind every check.  Device form: the caller's pointers as they are, the launch, a wait unless NO_WAIT.
-// Host form: the segments laid out in the order given in the session's scratch -- one buffer for the four families, grown
+// Host form: the segments laid out in the order given in the session's scratch -- one buffer for the five families, grown
 // only for a larger call than any before --, the input up if it has bytes, the launch, the outputs down in the order given,
 // a wait.  All of it on the session's stream behind every band launch so far.
 template <size_t N, class Launch>
@@ -232,6 +234,49 @@ void session_clearance(f3d_session &s, const f3d_session_clearance_desc &q) {
     raster_run(s, q.flags, "clearance", "clearance kernel", segments, [&] { return launch_clearance(R, s.stream); });
 }
 
+void session_umbra(f3d_session &s, const f3d_session_umbra_desc &q) {
+    static_assert(F3D_UMBRA_DEVICE_POINTERS == kDevicePointers && F3D_UMBRA_NO_WAIT == kNoWait, "one DEVICE_POINTERS and one NO_WAIT for every family");
+    const bool device_form = raster_front(q, "f3d_session_umbra_desc", "umbra", F3D_UMBRA_CURVED | F3D_UMBRA_DEVICE_POINTERS | F3D_UMBRA_NO_WAIT | F3D_UMBRA_SESSION_SUN,
+                                          "2 CURVED, 4 DEVICE_POINTERS, 8 NO_WAIT, 16 SESSION_SUN");
+    const bool session_sun = (q.flags & F3D_UMBRA_SESSION_SUN) != 0u;
+    if (session_sun && (q.direction_count != 0u || q.directions))
+        fail(F3D_STATUS_VALUE, "SESSION_SUN is the session's own sun direction: it takes no directions (got %u)", q.direction_count);
+    raster_region(s, q, "umbra");
+    if (!session_sun && q.direction_count == 0u) fail(F3D_STATUS_VALUE, "an umbra raster needs at least one direction, or SESSION_SUN");
+    if (!session_sun && !q.directions) fail(F3D_STATUS_VALUE, "null directions for an umbra raster of %u", q.direction_count);
+    if (!q.depth && !q.deepest) fail(F3D_STATUS_VALUE, "an umbra raster needs an output: depth and deepest are both null");
+    const uint32_t k = session_sun ? 1u : q.direction_count;
+    if (!session_sun && !device_form)  // (a device call's lanes answer such a direction NaN: f3d_umbra.h)
+        for (uint32_t a = 0; a < k; a++) {
+            const float *d = q.directions + 4u * (size_t)a;
+            if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2]) || (d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f) || !(d[3] == 0.0f))
+                fail(F3D_STATUS_VALUE, "umbra direction %u is not a finite, non-zero (dx, dy, dz, 0)", a);
+        }
+
+    UmbraParams R{};
+    R.terrain = s.params.terrain;
+    R.curved = (q.flags & F3D_UMBRA_CURVED) ? 1u : 0u;
+    R.row0 = q.row0;
+    R.col0 = q.col0;
+    R.rows = q.rows;
+    R.cols = q.cols;
+    R.direction_count = k;
+    R.step_cap = horizon_step_cap(R.terrain);
+    R.sun = s.params.light.wi;  // (what k_raster reads for SESSION_SUN)
+    // (F3D_UMBRA_BLOCK=0: A/B switch, a wave owns 64 consecutive samples of the region instead of an 8 x 8 block -- same
+    // results; profiles/README.md)
+    static const bool rows_footprint = [] {
+        const char *e = getenv("F3D_UMBRA_BLOCK");
+        return e && e[0] == '0';
+    }();
+    R.block = rows_footprint ? 0u : 1u;
+    const uint64_t n = (uint64_t)q.rows * q.cols;
+    // the planes, then deepest, then the directions (16 bytes each; none: the session's sun)
+    RasterSegment segments[] = {raster_output(q.depth, k * n * 4u, R.depth), raster_output(q.deepest, n * 4u, R.deepest),
+                                raster_input(q.directions, session_sun ? 0u : (uint64_t)k * 16u, R.directions)};
+    raster_run(s, q.flags, "umbra", "umbra kernel", segments, [&] { return launch_umbra(R, s.stream); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -250,6 +295,10 @@ int f3d_session_irradiation(f3d_session *s, const f3d_session_irradiation_desc *
 
 int f3d_session_clearance(f3d_session *s, const f3d_session_clearance_desc *desc, char *err, size_t errlen) {
     return update_entry(s, desc, "clearance", session_clearance, err, errlen);
+}
+
+int f3d_session_umbra(f3d_session *s, const f3d_session_umbra_desc *desc, char *err, size_t errlen) {
+    return update_entry(s, desc, "umbra", session_umbra, err, errlen);
 }
 
 }  // extern "C"

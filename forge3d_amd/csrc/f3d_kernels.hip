@@ -232,6 +232,13 @@ hipError_t launch_clearance(const ClearanceParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(k_clearance, dim3(waves), dim3(kWave), 0, stream, p);
     return hipGetLastError();
 }
+hipError_t launch_umbra(const UmbraParams &p, hipStream_t stream) {
+    const uint32_t total = p.rows * p.cols;
+    if (total == 0u || p.direction_count == 0u) return hipSuccess;
+    const uint32_t waves = p.block ? ((p.cols + 7u) >> 3) * ((p.rows + 7u) >> 3) : (total + kWave - 1u) / kWave;
+    hipLaunchKernelGGL(k_umbra, dim3(waves), dim3(kWave), 0, stream, p);
+    return hipGetLastError();
+}
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream) {
     dim3 block(16, 16), grid((p.leaf_dim_x + 15) / 16, (p.leaf_dim_y + 15) / 16);
     hipLaunchKernelGGL(k_leaf_build, grid, block, 0, stream, p);

@@ -53,6 +53,7 @@ hipError_t launch_raster(const RasterParams &p, hipStream_t stream);  // DEM vis
 hipError_t launch_horizon(const HorizonParams &p, hipStream_t stream);  // horizon rasters (f3d_horizon.h), one lane a DEM sample
 hipError_t launch_irradiation(const IrradiationParams &p, hipStream_t stream);  // irradiation rasters (f3d_irradiation.h), 64 consecutive samples a workgroup
 hipError_t launch_clearance(const ClearanceParams &p, hipStream_t stream);  // clearance rasters (f3d_clearance.h), one lane a DEM sample
+hipError_t launch_umbra(const UmbraParams &p, hipStream_t stream);  // shadow-depth rasters (f3d_umbra.h), one lane a DEM sample
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream);
 hipError_t launch_level_build(const LevelBuildParams &p, hipStream_t stream);
 hipError_t launch_band_build(const BandBuildParams &p, hipStream_t stream);

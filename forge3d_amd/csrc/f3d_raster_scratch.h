@@ -1,9 +1,10 @@
 // f3d_raster_scratch.h -- where the pieces of a host-form raster call lie in the session's scratch: plain arithmetic, no HIP
 // type (tests/raster_scratch_host compiles it alone).  A call is an ordered list of segments -- its outputs and its one input;
 // they are laid out in the order given, back to back, and the input starts on a multiple of 16 (its rows are read as float4
-// or float2).  An absent segment has 0 bytes: it takes no room, but an input still rounds.  The four lists (f3d_host_rasters.h):
+// or float2).  An absent segment has 0 bytes: it takes no room, but an input still rounds.  The five lists (f3d_host_rasters.h):
 //   raster       masks, [targets], count            horizon    planes, sky_view, [azimuths]
 //   irradiation  energy, count, normals, [directions]   clearance  planes, lowest, [observers]
+//   umbra        planes, deepest, [directions]
 #pragma once
 
 #include <cstddef>

@@ -347,4 +347,19 @@ struct ClearanceParams {
     float *lowest;               // rows * cols: the minimum over the observers
 };
 
+// Shadow-depth rasters on a live session (f3d_session_umbra; k_umbra, f3d_umbra.h): terrain only, one lane a DEM sample of the
+// region, a loop over the directions.  Either output may be null.
+struct UmbraParams {
+    TerrainDev terrain;
+    uint32_t curved;             // the sun rays' curvature policy, as an ALONG_DIRECTION raster's
+    uint32_t row0, col0, rows, cols;  // the region, as a raster's
+    uint32_t direction_count;    // >= 1
+    uint32_t step_cap;           // horizon_step_cap(terrain)
+    uint32_t block;              // a wave's footprint: 0 = 64 consecutive samples of the region, 1 = an 8 x 8 block of it
+    V3 sun;                      // directions null: the one direction, the session's sun as the frames' sun rays use it (SESSION_SUN)
+    const float4 *directions;    // (dx, dy, dz, 0) each: toward the light; null: sun
+    float *depth;                // direction_count x rows * cols
+    float *deepest;              // rows * cols: the maximum over the directions
+};
+
 }  // namespace f3d

@@ -739,6 +739,62 @@ class TerrainSession:
             return np.full((rows, cols), np.inf, np.float32)
         return self.clearance(observers, curved=curved, region=region, planes=False, lowest=True)
 
+    # -- shadow-depth rasters: the height needed to be lit --------------------------------------
+    def umbra(self, directions=None, *, curved: bool = True, region=None, planes: bool = True, deepest: bool = False, wait: bool = True):
+        """One f3d_session_umbra: for every DEM sample of ``region`` (``(row0, col0, rows, cols)``, default the whole DEM) and
+        every direction, how far above the ground a point over the sample must stand to be lit from that direction -- the
+        smallest ``lift`` at which ``visibility(direction, toward=False, lift=lift, terrain_only=True)`` answers True, as one
+        bounded walk of the session's min/max pyramid (terrain only: a mesh casts no shadow here).  ``directions`` (K, 4)
+        float32 rows ``(dx, dy, dz, 0)`` ((K, 3): the fourth is 0), toward the light, used as given; ``None`` is the session's
+        current sun, as the frames' sun rays use it.  0: the ground itself is lit; +inf: straight down; NaN: a non-finite or
+        zero direction handed in as a tensor.  ``dy <= 0`` is legal (the DEM's footprint is finite).  ``curved``: the rays follow
+        the session's earth curvature, as shadow_mask()'s.  A NumPy array (or None) takes the host form (blocking); a torch
+        tensor on the session's device the device form (results are tensors; ``wait=False`` returns with the kernel in flight
+        on the session's stream).
+        Returns the float32 array (K, rows, cols) for ``planes``, the float32 array (rows, cols) of the maximum over the
+        directions ("lit from all of them above this"; the K planes are then never materialised) for ``deepest``,
+        ``(planes, deepest)`` for both.  ``shadow_mask(d) == (lit_height(d) < SURFACE_BIAS)`` away from a band of rounding
+        around the threshold."""
+        if not (planes or deepest):
+            raise ValueError("umbra() needs an output: planes, deepest or both")
+        region = self._region(region)
+        rows, cols = region[2:]
+        device = _form(directions, wait, "umbra", "umbras")
+        q = _native.UmbraDesc()
+        q.flags = _native.UMBRA_CURVED if curved else 0
+        if directions is None:
+            q.flags |= _native.UMBRA_SESSION_SUN
+            t, k = None, 1
+        else:
+            t = _rows4(directions, device)
+            k = q.direction_count = int(t.shape[0])
+        p_out, d_out = _output(device, planes, (k, rows, cols), np.float32), _output(device, deepest, (rows, cols), np.float32)
+        self._call(self._lib.f3d_session_umbra, q, device, wait, region, "directions", t, (("depth", p_out), ("deepest", d_out)))
+        return (p_out, d_out) if (planes and deepest) else (p_out if planes else d_out)
+
+    def lit_height(self, direction=None, *, curved: bool = True, region=None):
+        """How high above the ground must a point over each DEM sample stand to be lit?  ``direction``: one ``(x, y, z)`` toward
+        the light (None: the session's current sun), or a track (N, 3): then the height above which the sample is lit from
+        EVERY position of the track.  A position with ``y <= 0`` (the sun below the horizontal) is dropped, as sun_hours()
+        drops it; an empty track returns zeros.  Returns the float32 array (rows, cols): 0 where the ground itself is lit.
+        ``shadow_mask(d) == (lit_height(d) < SURFACE_BIAS)`` away from a band of rounding around the threshold (terrain only:
+        a mesh casts no shadow here)."""
+        if direction is None:
+            return self.umbra(None, curved=curved, region=region)[0]
+        d = np.asarray(direction, dtype=np.float32)
+        if d.ndim == 1:
+            d = d.reshape(1, -1)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError(f"expected a direction (x, y, z) or a track of shape (N, 3), got {np.asarray(direction).shape}")
+        d = d[d[:, 1] > 0.0]
+        if len(d) == 0:
+            row0, col0, rows, cols = self._region(region)
+            dem_h, dem_w = self.dem_shape
+            if min(rows, cols) <= 0 or row0 + rows > dem_h or col0 + cols > dem_w:
+                raise ValueError(f"region=(row0, col0, rows, cols)={tuple(region)} is empty or reaches outside the {dem_h}x{dem_w} DEM")
+            return np.zeros((rows, cols), np.float32)
+        return self.umbra(d, curved=curved, region=region, planes=False, deepest=True)
+
     # -- irradiation rasters: beam energy over a sun track, surface normals --------------------
     @staticmethod
     def irradiation_terms(directions, weights=None):

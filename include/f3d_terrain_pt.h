@@ -661,6 +661,53 @@ typedef struct f3d_session_clearance_desc {
     uint32_t reserved;        /* 0 */
 } f3d_session_clearance_desc;
 int f3d_session_clearance(f3d_session *session, const f3d_session_clearance_desc *desc, char *err, size_t errlen);
+/* ---- shadow-depth rasters: the height needed to be lit ------------------------------------------------------------------------
+ * For every DEM sample of a region and every direction toward a light, how far above the GROUND a point over that sample must
+ * stand to be lit from it -- the mounting height at which a panel or a mast catches the sun, the top of the terrain's shadow
+ * volume: one pass is the sun mask for every lift at once (terrain only: a session with a mesh answers for its terrain).  One
+ * bounded walk of the min/max pyramid per sample per direction, from the sample (k_umbra; the contract, the leaf's closed form
+ * and the bound are at the head of csrc/f3d_umbra.h).  The sample's lattice point g = (g.x, h, g.z) is the visibility rasters'
+ * with lift 0; a direction is four f32 (dx, dy, dz, w), used as given, as an ALONG_DIRECTION target of f3d_session_raster; w is
+ * reserved: 0.  With k = (dx dx + dz dz) inv_two_r_prime with CURVED on a scene with earth curvature (else 0),
+ * p(t) = (g.x + t dx, g.z + t dz) and y the bilinear surface,
+ *     L* = max(+0, sup over t > 0, p(t) inside the footprint, of y(p(t)) - k t^2 - dy t - h)
+ * is the smallest lift at which the ALONG_DIRECTION raster's ray from the sample is unblocked under the same flag.  dy <= 0 is
+ * legal: the footprint is finite.
+ *   0     the ground itself is lit: no terrain along the direction, or none high enough; dx == dz == 0 and dy > 0
+ *   +inf  dx == dz == 0 and dy < 0
+ *   NaN   a walk that exceeds its step cap (no DEM does); in the device form a non-finite component, a zero direction, w != 0
+ * All arithmetic is f32, one rounding per operation.
+ *   depth    direction_count x rows * cols f32: plane k is direction k, sample n = r * cols + c
+ *   deepest  rows * cols f32: the maximum over the directions (above it the sample is lit from all of them), NaN planes ignored
+ * Either may be NULL, not both; with depth NULL nothing of size direction_count x rows * cols is written or allocated.
+ * SESSION_SUN (direction_count 0, directions NULL): one plane, the direction the frames' sun rays use NOW, as
+ * F3D_RASTER_SESSION_SUN.  CURVED, DEVICE_POINTERS, NO_WAIT and the ordering on the session stream are the raster's; nothing a
+ * frame launch reads is written.
+ *   host pointers (default)  blocking; staged through the visibility rasters' scratch buffer (the outputs asked for + 16 bytes
+ *       a direction), grown only for a larger call than any before, against memory_budget_bytes (too small: status 2, session
+ *       unchanged).  A non-finite component, a zero direction or w != 0: refused
+ *   DEVICE_POINTERS          directions (16-byte aligned), depth and deepest are device memory; nothing is copied or allocated.
+ * Refused (status 1, session unchanged), in this order: an unknown flag, reserved != 0, NO_WAIT without DEVICE_POINTERS,
+ * SESSION_SUN with directions, a region that is empty or reaches outside the DEM, direction_count 0 without SESSION_SUN, NULL
+ * directions, both outputs NULL.  No ABI version bump: detected by the symbol f3d_session_umbra. */
+#define F3D_UMBRA_CURVED 2u
+#define F3D_UMBRA_DEVICE_POINTERS 4u
+#define F3D_UMBRA_NO_WAIT 8u
+#define F3D_UMBRA_SESSION_SUN 16u
+typedef struct f3d_session_umbra_desc {
+    uint32_t struct_size;      /* = sizeof(f3d_session_umbra_desc) of the caller's header */
+    uint32_t flags;            /* F3D_UMBRA_CURVED | _DEVICE_POINTERS | _NO_WAIT | _SESSION_SUN */
+    uint32_t row0;             /* the region, in DEM samples: rows [row0, row0 + rows), columns [col0, col0 + cols) */
+    uint32_t col0;
+    uint32_t rows;
+    uint32_t cols;
+    uint32_t direction_count;  /* >= 1; 0 with SESSION_SUN */
+    uint32_t reserved;         /* 0 */
+    const float *directions;   /* direction_count x 4 f32: (dx, dy, dz, 0); NULL with SESSION_SUN */
+    float *depth;              /* direction_count x rows * cols, or NULL */
+    float *deepest;            /* rows * cols, or NULL */
+} f3d_session_umbra_desc;
+int f3d_session_umbra(f3d_session *session, const f3d_session_umbra_desc *desc, char *err, size_t errlen);
 /* ---- drape: an image laid over the terrain, per-texel albedo ---------------------------------------------------------------
  * What an image changes on top of a re-aim, still without a new session: the albedo of TERRAIN hits.  The drape is
  * image[rows][cols] of linear RGB reflectances, f32, row-major, `channels` (3 or 4; a fourth channel is ignored) values a
