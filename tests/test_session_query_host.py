@@ -28,6 +28,7 @@ import scenes
 from emul import emul
 from oracle import oracle
 from test_session_rearm_host import _desc
+from trace_reference import triangle_search
 
 ROOT = Path(__file__).resolve().parent.parent
 HARNESS = ROOT / "tests" / "query_host" / "query_harness.cpp"
@@ -155,8 +156,8 @@ def _ground_points(dem, spacing, n=4000, seed=20250):
 
 def test_ground_equals_the_oracle_bit_for_bit(harness):
     """top - t of 4 000 vertical rays from top = max * exaggeration + 10 equals the oracle's, bit for bit; NaN outside the
-    footprint.  Printed, not gated: how far those heights are from the f64 bilinear patch (measured on the oracle: 7.2e-6 at
-    relief 20, about 4 ulp of top = 30; the rounding of top - t, not of the intersection)."""
+    footprint.  Gated at 8 ulp(top): how far those heights are from the f64 bilinear patch (measured on the oracle: 7.2e-6 at
+    relief 20, about 4 ulp of top = 30; the rounding of top - t, not of the intersection; the factor 2 is for more relief)."""
     dem = scenes.golden_dem(4)
     kw = _kw(dem)
     spacing = kw["spacing"][0]
@@ -184,6 +185,7 @@ def test_ground_equals_the_oracle_bit_for_bit(harness):
         ref = (z[j, i] * (1 - a) + z[j, i + 1] * a) * (1 - b) + (z[j + 1, i] * (1 - a) + z[j + 1, i + 1] * a) * b
         err = np.abs(y_got[:n_inner].astype(np.float64) - ref)
         print(f"ground: max |top - t - bilinear_f64| = {err.max():.3g} (top = {float(top):g}, ulp(top) = {float(np.spacing(top)):.3g})")
+        assert err.max() <= 8 * float(np.spacing(top)), "each of the two subtractions rounds once at the magnitude of top"
     finally:
         scene.close()
 
@@ -288,21 +290,8 @@ def test_primitive_names_what_was_hit(city):
     got = forms[2].run(0, rays)
     mesh = got["kind"] == 2
     assert mesh.sum() >= 1575
-    # f64 Moeller-Trumbore over all triangles
-    o, d = rays[mesh, 0:3].astype(np.float64)[:, None, :], rays[mesh, 4:7].astype(np.float64)[:, None, :]
-    v0, v1, v2 = (verts[tris[:, k]].astype(np.float64)[None, :, :] for k in range(3))
-    e1, e2 = v1 - v0, v2 - v0
-    hh = np.cross(d, e2)
-    a = (e1 * hh).sum(-1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        f = 1.0 / a
-        s = o - v0
-        u = f * (s * hh).sum(-1)
-        q = np.cross(s, e1)
-        v = f * (d * q).sum(-1)
-        t = f * (e2 * q).sum(-1)
-        ok = (np.abs(a) >= 1e-7) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (t > 1e-3)
-    t = np.where(ok, t, np.inf)
+    # f64 Moeller-Trumbore over all triangles (tests/trace_reference.py)
+    t, _, _, _ = triangle_search(verts, tris, rays[mesh])
     order = np.argsort(t, axis=1)
     rows = np.arange(len(t))
     t0, t1 = t[rows, order[:, 0]], t[rows, order[:, 1]]
