@@ -249,6 +249,22 @@ DRAPE_MAX_SIDE = 16384  # F3D_DRAPE_MAX_SIDE
 DRAPE_TEXEL_MAX = 65504.0  # the largest finite binary16
 
 
+class PaintDesc(C.Structure):
+    """f3d_session_paint_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("primitive", C.c_uint32), ("vertex_count", C.c_uint32),
+        ("xz", C.c_void_p), ("rgba", C.c_void_p), ("feature", C.c_void_p),
+        ("indices", C.c_void_p), ("index_count", C.c_uint32),
+        ("half_width", C.c_float), ("opacity", C.c_float),
+        ("aim", ReaimDesc),
+    ]
+
+
+PAINT_POINTS, PAINT_LINES, PAINT_TRIANGLES = 0, 1, 2
+PAINT_MAX_PRIMITIVES = 1 << 24  # F3D_PAINT_MAX_PRIMITIVES
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -295,6 +311,9 @@ ABI = [
     ("f3d_session_umbra", C.c_int, [C.c_void_p, _P(UmbraDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape", C.c_int, [C.c_void_p, _P(DrapeDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
+    ("f3d_session_paint", C.c_int, [C.c_void_p, _P(PaintDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_paint_stats", C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint64)]),
+    ("f3d_session_drape_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_void_p, C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_sky_blocks", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_debug_wave_times", C.c_int, [C.c_void_p, C.c_void_p]),
@@ -364,7 +383,7 @@ KERNEL_FLAGS = [
     # default is now 1.1 % FASTER, 8 690 -> 8 785 Msamples/s in one call, same image; profiles/r04_variant_ab.log)
 ]
 HIP_SOURCES = ["f3d_kernels.hip", "f3d_host.hip", "f3d_denoise.hip", "f3d_smoke.hip", "f3d_smoke_sim.hip", "f3d_composite.hip", "f3d_lbvh.hip", "f3d_bvh_refit.hip", "f3d_retable.hip", "f3d_wavefront.hip",
-               "f3d_aether_bake.hip", "f3d_aether_ref.hip"]
+               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip"]
 
 
 def source_digest() -> str:

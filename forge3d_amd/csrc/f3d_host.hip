@@ -144,6 +144,22 @@ struct f3d_session {
         float *staging = nullptr;
         uint64_t staging_bytes = 0;
     } drape;
+    // paint (f3d_session_paint): the primitive records with the binning's counters, and the keys with the sort's storage and
+    // the run list -- each grown only, for a larger call than any before, and given back with the drape
+    struct Paint {
+        void *prims = nullptr, *keys = nullptr;
+        uint64_t prim_bytes = 0, key_bytes = 0;
+        // the last call (f3d_session_paint_stats): a pair of events around each of its three device steps, and what it counted
+        hipEvent_t mark[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        uint64_t last[3] = {0, 0, 0};  // primitives, (tile, primitive) keys, tiles painted
+        bool timed = false;
+        void release(Ledger &mem) {
+            if (prims) mem.free(prims, (size_t)prim_bytes);
+            if (keys) mem.free(keys, (size_t)key_bytes);
+            prims = keys = nullptr;
+            prim_bytes = key_bytes = 0;
+        }
+    } paint;
     TerrainTables tables;
     uint32_t width = 0, height = 0, row_begin = 0, row_end = 0, rows = 0;
     PackedReservoir *res[2] = {nullptr, nullptr};
@@ -214,6 +230,8 @@ struct f3d_session {
             for (hipEvent_t e : b.done)
                 if (e) (void)hipEventDestroy(e);
         if (fork) (void)hipEventDestroy(fork);
+        for (hipEvent_t e : paint.mark)
+            if (e) (void)hipEventDestroy(e);
         for (hipStream_t st : band_streams) (void)hipStreamDestroy(st);
         if (host_stats) (void)hipHostFree(host_stats);
         for (auto &link : peer)
@@ -1003,6 +1021,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 #include "f3d_host_query.h"  // ray queries on a live session: checks, scratch, staged copies, launch and their C ABI
 #include "f3d_host_rasters.h"  // visibility, horizon, irradiation, clearance and shadow-depth rasters on a live session: one path, their own steps and their C ABI
 #include "f3d_host_drape.h"  // an image draped over the terrain of a live session: checks, buffer, staged upload, packing and its C ABI
+#include "f3d_host_paint.h"  // vector features painted into that drape: checks, records, binning, the paint kernel, the read-back and their C ABI
 
 // ---------------------------------------------------------------------------------------
 // C ABI

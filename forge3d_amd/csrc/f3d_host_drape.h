@@ -62,6 +62,7 @@ void session_drape(f3d_session &s, const f3d_session_drape_desc &q) {
             s.params.drape = nullptr;
             s.mem.free(D.buffer, (size_t)D.bytes);
             if (D.staging) s.mem.free(D.staging, (size_t)D.staging_bytes);
+            s.paint.release(s.mem);  // (f3d_session_paint's buffers go with the canvas)
             D = f3d_session::Drape{};
         }
         u.apply();

@@ -124,7 +124,8 @@ void check_budget(const f3d_session &s, uint64_t planned, const char *update, co
 }
 
 // A scratch of the session that only grows (the query's, the rasters'): for a call that wants more than it holds, the larger
-// buffer is taken and committed, then the old one goes back -- nothing is in flight on it, the host forms are blocking.
+// buffer is taken and committed, then the old one goes back -- nothing is in flight on it for the blocking host forms; a paint
+// (f3d_host_paint.h) returns with kernels enqueued on its buffers and relies on Ledger::free waiting for the device.
 void grow_scratch(f3d_session &s, void *&scratch, uint64_t &bytes, uint64_t want, const char *noun, const char *brings, const char *what) {
     if (want <= bytes) return;
     check_budget(s, s.mem.device_bytes - bytes + want, noun, brings);

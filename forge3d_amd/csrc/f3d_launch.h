@@ -6,6 +6,7 @@
 #include "f3d_aether.h"
 #include "f3d_build.h"
 #include "f3d_drape.h"
+#include "f3d_paint.h"
 #include "f3d_scene.h"
 
 namespace f3d {
@@ -47,6 +48,14 @@ hipError_t launch_rearm(const RearmParams &p, hipStream_t stream);  // same grid
 hipError_t launch_reaim(const RearmParams &p, hipStream_t stream);  // ... and its LDS: the G-buffer pass and the re-arm in one
 hipError_t launch_resolve(const ResolveParams &p, hipStream_t stream);  // (a draped session: the draped resolve)
 hipError_t launch_drape_pack(const DrapePackParams &p, hipStream_t stream);  // f32 texels into a session's binary16 drape (f3d_drape.h)
+// vector features into a session's drape (f3d_paint.h, f3d_paint.hip): the temporary storage of the scan over prim_count + 1
+// counts and of the key sort; count pass + scan (offsets[prim_count] = the number of keys); emit + sort + run list (P.keys,
+// P.sorted: key_count words each, P.runs: min(key_count, tiles) words, P.run_count: one); k_paint over run_count tiles
+hipError_t paint_scan_bytes(uint32_t prim_count, size_t *bytes);
+hipError_t paint_sort_bytes(uint32_t key_count, uint32_t tiles, size_t *bytes);
+hipError_t launch_paint_count(const PaintParams &p, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
+hipError_t launch_paint_bin(const PaintParams &p, uint32_t tiles, void *sort_tmp, size_t sort_bytes, hipStream_t stream);
+hipError_t launch_paint(const PaintParams &p, uint32_t run_count, hipStream_t stream);
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream);
 hipError_t launch_query(const QueryParams &p, hipStream_t stream);  // ray queries on a live session (f3d_query.h), 64 rays a workgroup
 hipError_t launch_raster(const RasterParams &p, hipStream_t stream);  // DEM visibility rasters (f3d_raster.h), 64 consecutive samples a workgroup

@@ -354,6 +354,112 @@ class TerrainSession:
         names = {v: k for k, v in self.DRAPE_FILTERS.items()}
         return {"rows": int(info[0]), "cols": int(info[1]), "filter": names[int(info[2])], "bytes": int(info[3])}
 
+    # -- paint: vector features composited into the drape, on the GPU ---------------------------------
+    PAINT_PRIMITIVES = {"points": _native.PAINT_POINTS, "lines": _native.PAINT_LINES, "triangles": _native.PAINT_TRIANGLES}
+
+    @staticmethod
+    def paint_indices(count: int, primitive: str):
+        """The index list ``indices=None`` stands for over ``count`` vertices: every vertex for points, one strip for lines,
+        consecutive triples for triangles."""
+        if primitive == "lines":
+            i = np.arange(max(count - 1, 0), dtype=np.uint32)
+            return np.stack([i, i + np.uint32(1)], 1).ravel()
+        return np.arange(count - (count % 3 if primitive == "triangles" else 0), dtype=np.uint32)
+
+    def paint(self, xz, rgba, indices=None, *, primitive="lines", width=1.0, opacity=1.0, features=None, camera=None, **rearmable):
+        """reaim() over a drape with vector features painted into it: roads, rivers, parcels, tracks, markers, rasterised on the
+        GPU into the session's drape (drape() gives the canvas first), which the frames then sample as before.  ``xz`` is
+        ``(N, 2)`` world x, z; ``rgba`` one colour or ``(N, 4)`` colours, linear RGB reflectance and alpha in [0, 1] (three numbers:
+        alpha 1); ``indices`` index the vertices, 1 / 2 / 3 a primitive (``None``: see paint_indices()).  ``primitive``:
+        ``"lines"`` -- strokes ``width`` metres wide with round caps and joins and a one-texel edge ramp, ``"points"`` -- discs of
+        diameter ``width``, ``"triangles"`` -- filled, watertight across shared edges.  ``features`` is ``(N,)`` feature ids: a run
+        of consecutive primitives whose first vertices carry one id is one feature and blends once (no darker joints under
+        ``opacity`` < 1); without ids the whole call is one feature.  Features blend in list order, the later over the earlier.
+        Coordinates lie within 65536 canvas texels of the terrain's centre (the world's origin): the reach the rasteriser's f32
+        distances are sized for; clip far geometry to the terrain's neighbourhood.
+        ``camera`` and the other values as reaim() takes them.  Same contract as drape(): the render restarts at frame 0 and a
+        refused value leaves the session, and the canvas, as they were."""
+        self._known("paint", rearmable)
+        if primitive not in self.PAINT_PRIMITIVES:
+            raise ValueError(f"primitive must be 'points', 'lines' or 'triangles', got {primitive!r}")
+        pts = np.ascontiguousarray(xz, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] == 0:
+            raise ValueError(f"xz must have shape (N, 2) with N >= 1, got {pts.shape}")
+        n = pts.shape[0]
+        col = np.asarray(rgba, dtype=np.float32)
+        if col.ndim == 1 and col.shape[0] in (3, 4):
+            col = np.broadcast_to(col, (n, col.shape[0]))
+        if col.ndim != 2 or col.shape[0] != n or col.shape[1] not in (3, 4):
+            raise ValueError(f"rgba must be one colour of 3 or 4 numbers or have shape ({n}, 3|4), got {np.shape(rgba)}")
+        if col.shape[1] == 3:
+            col = np.concatenate([col, np.ones((n, 1), np.float32)], 1)
+        col = np.ascontiguousarray(col, dtype=np.float32)
+        per = self.PAINT_PRIMITIVES[primitive] + 1
+        if indices is None:
+            idx = self.paint_indices(n, primitive)
+        else:
+            raw = np.asarray(indices)
+            if raw.dtype.kind not in "iu":
+                raise ValueError(f"indices must be integers, got {raw.dtype}")
+            if raw.size and int(raw.min()) < 0:
+                raise ValueError("indices must not be negative")
+            idx = np.ascontiguousarray(raw, dtype=np.uint32).ravel()
+        if idx.size == 0 or idx.size % per:
+            raise ValueError(f"{idx.size} indices do not make {primitive}: their count must be a positive multiple of {per}")
+        if idx.size // per > _native.PAINT_MAX_PRIMITIVES:
+            raise ValueError(f"a paint call takes at most {_native.PAINT_MAX_PRIMITIVES} primitives, got {idx.size // per}")
+        if int(idx.max()) >= n:
+            raise ValueError(f"index {int(idx.max())} is out of range: the call has {n} vertices")
+        width, opacity = float(width), float(opacity)
+        if not np.isfinite(width) or width < 0.0:
+            raise ValueError(f"width must be finite and >= 0 metres, got {width}")
+        if not 0.0 <= opacity <= 1.0:
+            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+        ids = None
+        if features is not None:
+            raw = np.asarray(features)
+            if raw.shape != (n,) or raw.dtype.kind not in "iu" or (raw.size and int(raw.min()) < 0):
+                raise ValueError(f"features must be ({n},) non-negative integers, got shape {raw.shape} of {raw.dtype}")
+            ids = np.ascontiguousarray(raw, dtype=np.uint32)
+        q = _native.PaintDesc()
+        q.struct_size = C.sizeof(_native.PaintDesc)
+        q.primitive = self.PAINT_PRIMITIVES[primitive]
+        q.vertex_count = n
+        q.xz, q.rgba = pts.ctypes.data, col.ctypes.data
+        q.feature = ids.ctypes.data if ids is not None else None
+        q.indices, q.index_count = idx.ctypes.data, idx.size
+        q.half_width = np.float32(width) * np.float32(0.5)
+        q.opacity = opacity
+        q.aim = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_paint, q, q.aim.arm, camera)  # (pts, col, ids and idx live until here)
+
+    def paint_stats(self):
+        """``None`` before the first paint(), else the last call's device times in ms (``count_ms``: count pass and scan,
+        ``bin_ms``: emit, sort and run list, ``paint_ms``: the paint kernel) and what it counted (``primitives``, ``keys``: the
+        (tile, primitive) pairs, ``tiles``: the non-empty tiles painted).  Waits for the call's kernels."""
+        ms, counts = (C.c_double * 3)(), (C.c_uint64 * 3)()
+        if not self._lib.f3d_session_paint_stats(self._handle, ms, counts):
+            return None
+        return {"count_ms": ms[0], "bin_ms": ms[1], "paint_ms": ms[2], "primitives": int(counts[0]), "keys": int(counts[1]), "tiles": int(counts[2])}
+
+    def drape_image(self, region=None):
+        """The session's drape as ``(rows, cols, 3)`` float32 linear RGB -- the values its binary16 texels hold -- after
+        everything enqueued on the session, paint() included: what a composed map is saved with.  ``region`` is
+        ``(row0, col0, rows, cols)`` in texels, default the whole drape."""
+        info = self.drape_info()
+        if info is None:
+            raise ValueError("this session has no drape to read")
+        if region is None:
+            reg, rows, cols = None, info["rows"], info["cols"]
+        else:
+            row0, col0, rows, cols = (int(v) for v in region)
+            if min(row0, col0, rows, cols) < 0:
+                raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+            reg = (C.c_uint32 * 4)(row0, col0, rows, cols)
+        out = np.zeros((rows, cols, 3), np.float32)
+        self._check(self._lib.f3d_session_drape_read(self._handle, reg, out.ctypes.data, self._err, len(self._err)))
+        return out
+
     # what the four updates share: the keyword check, the camera rule, the call with what the wrapper remembers of it
     def _known(self, method: str, rearmable: dict) -> None:
         unknown = [k for k in rearmable if k not in self.REARMABLE]

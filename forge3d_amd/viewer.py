@@ -8,8 +8,9 @@ offline render: ``open_viewer_async(width, height, terrain_path=..., fov_deg=...
 ``load_terrain``, ``set_orbit_camera``, ``set_camera_lookat``, ``set_fov``, ``set_sun``, ``set_sun_time``, ``set_ibl``,
 ``set_z_scale``, ``snapshot(path, width, height)``, ``render_animation``, ``get_stats``, ``close`` and the context
 manager.  There is no subprocess and no window: every snapshot is a converged path-traced frame on the MI355X.
-``load_overlay`` drapes ONE image over the terrain as its per-texel albedo (TerrainSession.drape).  Commands of the raster
-viewer that have no meaning offline (labels, vector overlays, point clouds) raise ``ViewerError`` instead of being ignored.
+``load_overlay`` drapes ONE image over the terrain as its per-texel albedo (TerrainSession.drape) and ``add_vector_overlay``
+paints points, lines and triangles into that drape on the GPU (TerrainSession.paint).  Commands of the raster viewer that
+have no meaning offline (labels, point clouds) raise ``ViewerError`` instead of being ignored.
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ class ViewerError(Exception):
 
 _RASTER_ONLY = ("load_obj", "load_gltf", "load_bundle", "load_point_cloud", "set_point_cloud_params",
                 "set_transform", "add_label", "add_labels", "add_line_label", "add_curved_label", "add_callout",
-                "add_vector_overlay", "set_labels_enabled", "clear_labels", "remove_label", "set_label_typography",
+                "set_labels_enabled", "clear_labels", "remove_label", "set_label_typography",
                 "set_declutter_algorithm", "poll_pick_events", "update_labels", "load_label_atlas",
                 "set_terrain_scatter", "clear_terrain_scatter", "apply_scene_variant", "set_review_layer_visible")
 
@@ -45,6 +46,9 @@ class ViewerHandle(OfflineTerrainViewer):
         self._revision = 0
         self._open = True
         self._overlay = None
+        self._vector_layers = {}
+        self._vector_next_id = 1
+        self._vector_canvas = None
 
     # -- scene --------------------------------------------------------------------------------------------
     def load_terrain(self, path: Union[str, Path, np.ndarray], spacing: Union[float, Tuple[float, float], None] = None) -> None:
@@ -149,10 +153,164 @@ class ViewerHandle(OfflineTerrainViewer):
         return (cols / ((dem_w - 1) * (u1 - u0)), -u0 * cols / (u1 - u0) - 0.5,
                 rows / ((dem_h - 1) * (v1 - v0)), -v0 * rows / (v1 - v0) - 0.5)
 
+    # -- vector overlays: painted into the drape (TerrainSession.paint) ------------------------------------------------
+    VECTOR_PRIMITIVES = ("points", "lines", "line_strip", "triangles", "triangle_strip")
+    VECTOR_CANVAS_TEXELS_PER_CELL, VECTOR_CANVAS_MAX_SIDE = 4, 8192
+
+    # what a row of add_vector_overlay can be refused for, in the order a row is looked at; the texts are the reference's
+    # (recorded in tests/golden/vector_overlay_messages.json)
+    VECTOR_VERTEX_REFUSALS = ("must contain exactly 8 lanes: XYZ, RGBA, feature ID", "XYZ must be finite f64",
+                              "RGBA must be finite values in [0, 1]", "feature ID must be an integer u32")
+
+    @staticmethod
+    def feature_id(value) -> Optional[int]:
+        """The feature id a vertex row's last lane stands for, or None when it is not a whole number in [0, 2^32) -- a bool, text
+        that is no number, None, a fraction, NaN, an infinity."""
+        if value is True or value is False:
+            return None
+        try:
+            number = float(value)
+        except (TypeError, ValueError):
+            return None
+        if not 0.0 <= number < 2.0 ** 32:  # (NaN compares false)
+            return None
+        whole = int(number)
+        return whole if whole == number else None
+
+    @classmethod
+    def vector_overlay_vertices(cls, vertices) -> np.ndarray:
+        """The rows of ``add_vector_overlay`` as an ``(N, 8)`` float64 array: eight lanes a row (X, Y, Z, R, G, B, A, feature
+        id), finite XYZ, RGBA in [0, 1], the id a whole number in [0, 2^32).  The first row that is not, and the first thing
+        wrong with it in that order, is refused with the reference's message for it."""
+        rows = list(vertices)
+        n = len(rows)
+        whole = np.array([len(row) == 8 for row in rows], bool).reshape(n)
+        ids = [cls.feature_id(row[7]) if ok else None for row, ok in zip(rows, whole)]
+        table = np.zeros((n, 8), np.float64)
+        if whole.any():
+            table[whole, :7] = np.array([list(row[:7]) for row, ok in zip(rows, whole) if ok], np.float64)
+        table[:, 7] = [0.0 if i is None else float(i) for i in ids]
+        rgba = table[:, 3:7]
+        with np.errstate(invalid="ignore"):
+            wrong = np.stack([~whole, ~np.isfinite(table[:, :3]).all(1), ~((rgba >= 0.0) & (rgba <= 1.0)).all(1),  # (NaN compares false)
+                              np.array([i is None for i in ids], bool).reshape(n)], 1)
+        bad_rows = np.flatnonzero(wrong.any(1))
+        if bad_rows.size:
+            row = int(bad_rows[0])
+            raise ValueError(f"vector vertex {row} {cls.VECTOR_VERTEX_REFUSALS[int(np.argmax(wrong[row]))]}")
+        return table
+
+    @staticmethod
+    def expand_strip(indices, primitive: str):
+        """(list primitive, index list) of ``primitive`` over ``indices``: ``line_strip`` becomes the segments (i, i + 1),
+        ``triangle_strip`` the triangles (i, i + 1, i + 2) with every second one's first two swapped (one winding); the list
+        kinds pass through."""
+        idx = np.asarray(indices, np.int64).ravel()
+        if primitive == "line_strip":
+            return "lines", np.stack([idx[:-1], idx[1:]], 1).ravel() if idx.size >= 2 else idx[:0]
+        if primitive == "triangle_strip":
+            if idx.size < 3:
+                return "triangles", idx[:0]
+            tri = np.stack([idx[:-2], idx[1:-1], idx[2:]], 1)
+            tri[1::2, :2] = tri[1::2, 1::-1]
+            return "triangles", tri.ravel()
+        return primitive, idx
+
+    def add_vector_overlay(self, name: str, vertices, indices, primitive: str = "triangles", drape: bool = True,
+                           drape_offset: float = 0.5, opacity: float = 1.0, depth_bias: float = 0.001, line_width: float = 2.0,
+                           point_size: float = 5.0, z_order: int = 0) -> int:
+        """reference viewer.py add_vector_overlay, as far as an offline path tracer has a counterpart: the layer is painted into
+        the terrain's drape on the GPU (TerrainSession.paint) by every later render() / snapshot() / render_animation(), lit
+        and shadowed like the ground it lies on.  ``vertices``: the reference's eight-lane rows (X, Y, Z, R, G, B, A, feature
+        id); under ``drape=True`` Y is ignored and X, Z are world x, z of the terrain (its centre is the origin).
+        ``drape=False`` -- an undraped 3-D overlay -- has no offline counterpart and raises.  ``primitive``: ``"points"``,
+        ``"lines"``, ``"line_strip"``, ``"triangles"`` or ``"triangle_strip"`` (strips are expanded to lists here).
+        ``line_width`` and ``point_size`` are in CANVAS TEXELS (the reference's are screen pixels, which an offline render of
+        any size and camera does not have); the canvas is the loaded overlay image, or else a constant image of the terrain's
+        albedo with four texels per DEM cell and axis (at most 8192 a side; set_vector_canvas overrides).  ``drape_offset`` and
+        ``depth_bias`` steer the raster viewer's depth test and are accepted and ignored.  Layers are painted in
+        ``(z_order, id)`` order.  Returns the layer's id."""
+        if not drape:
+            raise ViewerError("ViewerHandle.add_vector_overlay(drape=False) is an undraped 3-D overlay of the interactive raster viewer; "
+                              "the offline path tracer paints vector overlays into the terrain's drape only")
+        if primitive not in self.VECTOR_PRIMITIVES:
+            raise ViewerError(f"vector overlay primitive must be one of {', '.join(self.VECTOR_PRIMITIVES)}, got {primitive!r}")
+        rows = self.vector_overlay_vertices(vertices)
+        if rows.shape[0] == 0:
+            raise ViewerError("a vector overlay needs at least one vertex")
+        raw = [int(i) for i in indices]
+        if any(i < 0 or i >= rows.shape[0] for i in raw):
+            raise ViewerError(f"vector overlay indices must lie in [0, {rows.shape[0]})")
+        kind, idx = self.expand_strip(raw, str(primitive))
+        per = {"points": 1, "lines": 2, "triangles": 3}[kind]
+        if idx.size == 0 or idx.size % per:
+            raise ViewerError(f"{len(raw)} indices do not make {primitive}")
+        opacity, line_width, point_size = float(opacity), float(line_width), float(point_size)
+        if not 0.0 <= opacity <= 1.0:
+            raise ViewerError(f"vector overlay opacity must lie in [0, 1], got {opacity}")
+        if not (np.isfinite([line_width, point_size]).all() and line_width >= 0.0 and point_size >= 0.0):
+            raise ViewerError("vector overlay line_width and point_size must be finite and >= 0 canvas texels")
+        _ = drape_offset, depth_bias
+        layer_id = self._vector_next_id
+        self._vector_next_id = layer_id + 1
+        self._vector_layers[layer_id] = {"name": str(name), "xz": rows[:, [0, 2]].astype(np.float32), "rgba": rows[:, 3:7].astype(np.float32),
+                            "features": rows[:, 7].astype(np.uint32), "primitive": kind, "indices": idx.astype(np.uint32),
+                            "texels": point_size if kind == "points" else line_width, "opacity": opacity, "z_order": int(z_order)}
+        self._revision += 1
+        return layer_id
+
+    def remove_vector_overlay(self, overlay_id: int) -> None:
+        """Take the layer ``overlay_id`` (what add_vector_overlay returned) off again."""
+        if int(overlay_id) not in self._vector_layers:
+            raise ViewerError(f"no vector overlay with id {overlay_id}")
+        del self._vector_layers[int(overlay_id)]
+        self._revision += 1
+
+    def set_vector_canvas(self, rows: Optional[int], cols: Optional[int] = None) -> None:
+        """The size of the constant canvas vector overlays are painted into when no overlay image is loaded (``None``: the
+        default, four texels per DEM cell and axis, at most 8192 a side)."""
+        if rows is None:
+            self._vector_canvas = None
+        else:
+            rows, cols = int(rows), int(rows if cols is None else cols)
+            if not (1 <= rows <= 16384 and 1 <= cols <= 16384):
+                raise ViewerError(f"the vector canvas holds 1..16384 texels a side, got {rows} x {cols}")
+            self._vector_canvas = (rows, cols)
+        self._revision += 1
+
+    def vector_layers(self) -> list:
+        """The layers in the order they are painted: by ``(z_order, id)``."""
+        layers = self._vector_layers
+        return [layers[i] for i in sorted(layers, key=lambda i: (layers[i]["z_order"], i))]
+
+    def vector_canvas_shape(self, dem_shape) -> Tuple[int, int]:
+        if self._vector_canvas is not None:
+            return self._vector_canvas
+        k, cap = self.VECTOR_CANVAS_TEXELS_PER_CELL, self.VECTOR_CANVAS_MAX_SIDE
+        return (min(k * max(dem_shape[0] - 1, 1), cap), min(k * max(dem_shape[1] - 1, 1), cap))
+
+    def _paint_layers(self, s, keywords) -> None:
+        """Drape ``s`` with the constant canvas unless an overlay image is there already, then paint the layers."""
+        layers = self.vector_layers()
+        if not layers:
+            return
+        if not s.draped:
+            rows, cols = self.vector_canvas_shape(s.dem_shape)
+            albedo = np.asarray(keywords.get("albedo", (0.6, 0.6, 0.6)), np.float32)
+            s.drape(np.broadcast_to(albedo, (rows, cols, 3)), filter="bilinear", registration="area")
+        info = s.drape_info()
+        sx, _, sz, _ = (self.overlay_registration(s.dem_shape, self._overlay["image"].shape, self._overlay["extent"])
+                        if self._overlay is not None else s.drape_registration(info["rows"], info["cols"], "area"))
+        spacing = keywords.get("spacing", (1.0, 1.0))
+        texel = max(abs(float(spacing[0]) / float(sx)), abs(float(spacing[1]) / float(sz)))  # one canvas texel in metres
+        for layer in layers:
+            s.paint(layer["xz"], layer["rgba"], layer["indices"], primitive=layer["primitive"], width=layer["texels"] * texel,
+                    opacity=layer["opacity"], features=layer["features"])
+
     def render(self, width: Optional[int] = None, height: Optional[int] = None) -> dict:
-        """OfflineTerrainViewer.render; with an overlay loaded, the same loop on a session draped with it."""
+        """OfflineTerrainViewer.render; with an overlay or vector layers loaded, the same loop on a session draped with them."""
         overlay = getattr(self, "_overlay", None)
-        if overlay is None:
+        if overlay is None and not self.vector_layers():
             return super().render(width, height)
         dem, w, h, camera, keywords = self._call(width, height)
         with self._draped_session(dem, w, h, camera, keywords) as s:
@@ -160,14 +318,16 @@ class ViewerHandle(OfflineTerrainViewer):
         return self.last_result
 
     def _draped_session(self, dem, w, h, camera, keywords):
-        """A session of the viewer's scene, draped with the loaded overlay."""
+        """A session of the viewer's scene, draped with the loaded overlay, the vector layers painted over it."""
         from .session import TerrainSession
 
         overlay = self._overlay
         s = TerrainSession(dem, w, h, camera, **keywords)
         try:
-            reg = self.overlay_registration(s.dem_shape, overlay["image"].shape, overlay["extent"])
-            s.drape(overlay["image"], filter=overlay["filter"], registration=reg, srgb=overlay["srgb"])
+            if overlay is not None:
+                reg = self.overlay_registration(s.dem_shape, overlay["image"].shape, overlay["extent"])
+                s.drape(overlay["image"], filter=overlay["filter"], registration=reg, srgb=overlay["srgb"])
+            self._paint_layers(s, keywords)
         except Exception:
             s.close()
             raise
@@ -190,7 +350,7 @@ class ViewerHandle(OfflineTerrainViewer):
 
         out = Path(output_dir)
         out.mkdir(parents=True, exist_ok=True)
-        if self._overlay is not None:  # (a draped scene: ONE session draped with the overlay, re-aimed per key)
+        if self._overlay is not None or self.vector_layers():  # (a draped scene: ONE session draped and painted, re-aimed per key)
             session = None
             try:
                 for i, key in enumerate(animation):

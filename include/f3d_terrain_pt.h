@@ -773,6 +773,61 @@ typedef struct f3d_session_drape_desc {
 int f3d_session_drape(f3d_session *session, const f3d_session_drape_desc *desc, char *err, size_t errlen);
 /* Is the session draped?  info (may be NULL) = {rows, cols, filter, bytes of the drape buffer}; returns 1 / 0 (no session: 0). */
 int f3d_session_draped(f3d_session *session, uint32_t info[4]);
+
+/* ---- paint: vector features composited into the drape -----------------------------------------------------------------------
+ * Roads, rivers, parcels, tracks, summit markers: points, line segments or triangles in world x-z, rasterised on the device
+ * into the session's drape (the canvas), which the draped frames then sample as before.  No image crosses the bus: the call
+ * uploads the primitives only.  The per-texel rule is the opening comment of csrc/f3d_paint.h -- f32, one rounding per
+ * operation, independent of the tiling the device uses:
+ *   lines      index pairs; a stroke of half-width half_width metres with round caps and joins and a one-texel coverage ramp
+ *              (one texel = ramp = max(|spacing_x / scale_x|, |spacing_z / scale_z|) metres), colour and alpha lerped along it
+ *   points     single indices; the segment with both ends equal: a disc of radius half_width
+ *   triangles  index triples; coverage 1 or 0 at the texel centre with a top-left rule and edge functions that two triangles
+ *              sharing an edge evaluate to the same bits (a mesh is watertight: no gap, no texel blended twice); zero-area
+ *              triangles paint nothing; colour and alpha barycentric
+ * A run of consecutive primitives whose FIRST vertices carry one feature id is one feature: per texel its primitive with the
+ * highest coverage counts (ties: the lowest index), and it blends once,  dst += (opacity * alpha * cov) * (src - dst),  features
+ * in list order.  feature == NULL: the whole call is one feature.  Texels stay binary16: they are read, blended in f32 and
+ * written once per call; an untouched texel keeps its bits.
+ * An update like f3d_session_drape: ordered on the session stream behind everything enqueued, the render restarts at frame 0
+ * (aim: the camera and the re-armable members, as a re-aim takes them), every refusal comes before the first change, and the
+ * drape keeps its size, filter and registration.  The call waits for the device twice, for two counters (the number of
+ * (tile, primitive) pairs and of non-empty tiles), and returns with the paint kernel enqueued.
+ * Refused with status 1: a session without a drape; unknown flags or primitive; an index count that is no multiple of the
+ * primitive's (1, 2, 3) or zero; an index >= vertex_count; more than 2^24 primitives; a negative or non-finite half_width; an
+ * opacity outside [0, 1]; peer halos.  Status 3 (a host scan of all vertices): a non-finite coordinate; a coordinate more than
+ * 65536 texels (65536 ramp metres) from the terrain's centre, the world's origin -- the reach the f32 distances are sized for:
+ * clip far geometry to the terrain's neighbourhood --; an RGBA outside [0, 1].
+ * Status 2, the canvas unchanged: the primitive records (80 bytes each), the keys and the sort's storage do not fit
+ * memory_budget_bytes -- session buffers, tracked in gpu_resource_bytes, sized exactly after the count pass, grown only, freed
+ * with the drape.  The keys are sized after the count pass has run on the records' buffer: when THEY are refused that first
+ * buffer may have grown (gpu_resource_bytes with it); the canvas, the render state and f3d_session_fingerprint are as before. */
+#define F3D_PAINT_POINTS 0u
+#define F3D_PAINT_LINES 1u
+#define F3D_PAINT_TRIANGLES 2u
+#define F3D_PAINT_MAX_PRIMITIVES 16777216u
+typedef struct f3d_session_paint_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_paint_desc) of the caller's header */
+    uint32_t flags;              /* none defined: 0 */
+    uint32_t primitive;          /* F3D_PAINT_POINTS / _LINES / _TRIANGLES */
+    uint32_t vertex_count;       /* N */
+    const float *xz;             /* N x 2 f32: world x, z; host memory, read during the call only (as rgba, feature, indices) */
+    const float *rgba;           /* N x 4 f32 in [0, 1]: linear RGB reflectance and alpha */
+    const uint32_t *feature;     /* N feature ids, or NULL: one feature */
+    const uint32_t *indices;     /* index_count indices into the vertices: 1 / 2 / 3 a primitive */
+    uint32_t index_count;
+    float half_width;            /* metres: half the stroke width, the disc's radius; checked, not used, for triangles */
+    float opacity;               /* [0, 1] */
+    f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
+} f3d_session_paint_desc;
+int f3d_session_paint(f3d_session *session, const f3d_session_paint_desc *desc, char *err, size_t errlen);
+/* Diagnostics of the session's last paint call (tools/paint_time.py): ms = device time of {count pass + scan, emit + sort + run
+ * list, paint kernel} from events on the session stream (waits for them); counts = {primitives, (tile, primitive) keys, tiles
+ * painted}.  Either may be NULL.  Returns 1, or 0 when the session has not painted. */
+int f3d_session_paint_stats(f3d_session *session, double ms[3], uint64_t counts[3]);
+/* The drape's texels as f32 RGB in host memory, after everything enqueued on the session: region = {row0, col0, rows, cols} (NULL:
+ * the whole drape), rgb_out = rows x cols x 3 f32.  What a composed map is saved with.  Status 1: no drape, a region that leaves it. */
+int f3d_session_drape_read(f3d_session *session, const uint32_t region[4], float *rgb_out, char *err, size_t errlen);
 /* Memory / layout diagnostics of a session. */
 int f3d_session_info(f3d_session *session, uint64_t *gpu_resource_bytes, uint64_t *minmax_pyramid_bytes,
                      uint64_t *peak_host_visible_bytes, uint32_t *rows, uint32_t *width);
