@@ -4,8 +4,12 @@
 not needed).  Run here only -- /root/reference does not exist on the GPU box; the .npz travels.
 
     PYTHONPATH=/root/reference/python python tests/golden/make_denoise_fixtures.py
+
+Writes atrous_cases.npz (if it is not there; otherwise checks that it holds what this script computes) and
+atrous_edge_cases.npz.
 """
 import importlib.util
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -36,5 +40,38 @@ cases = {
 out = {"color": color, "albedo": albedo, "normal": normal, "depth": depth}
 for name, kw in cases.items():
     out["want_" + name] = ref.atrous_denoise(color, **kw)
-np.savez_compressed(Path(__file__).resolve().parent / "atrous_cases.npz", **out)
+here = Path(__file__).resolve().parent
+if (here / "atrous_cases.npz").exists():  # the committed file stays byte for byte (a .npz carries the time it was written)
+    z = np.load(here / "atrous_cases.npz")
+    assert sorted(z.files) == sorted(out) and all(np.array_equal(z[k], v) for k, v in out.items()), "atrous_cases.npz is not what this script writes"
+else:
+    np.savez_compressed(here / "atrous_cases.npz", **out)
 print({k: v.shape for k, v in out.items()})
+
+# ---- atrous_edge_cases.npz: the reference's outputs for the case table of tests/denoise_reference.py, wherever the reference
+# answers (the non-finite inputs included: the NaN contract is then the reference's own), and the dark image of the border case.
+# Where tests/denoise_reference.py says the reference does not answer, it must raise: its `_shift` cannot form the shift.
+sys.path.insert(0, str(here.parent))
+import denoise_reference as dr  # noqa: E402
+
+dark = dr.dark_image()
+edge, refused = {"dark_color": dark}, []
+with np.errstate(all="ignore"):
+    for case in dr.cases():
+        if case.get("committed"):
+            continue
+        c, kw = dr.inputs(case, dark)
+        if dr.reference_answers(*case["shape"], case["iterations"]):
+            edge["want_" + case["name"]] = ref.atrous_denoise(c, **kw)
+        else:
+            try:
+                ref.atrous_denoise(c, **kw)
+            except ValueError as e:
+                assert "could not broadcast" in str(e), e
+                refused.append(case["name"])
+            else:
+                raise AssertionError(case["name"] + ": the reference answered outside the domain denoise_reference.py states")
+np.savez_compressed(here / "atrous_edge_cases.npz", **edge)
+size = (here / "atrous_edge_cases.npz").stat().st_size
+assert size < (here / "atrous_cases.npz").stat().st_size, size
+print(f"atrous_edge_cases.npz: {len(edge) - 1} vectors, {size} bytes; the reference refused {len(refused)} cases: {refused}")
