@@ -35,6 +35,7 @@
 #pragma once
 
 #include "f3d_query.h"
+#include "f3d_walk.h"
 
 namespace f3d {
 
@@ -43,20 +44,9 @@ struct IrradiationSlope {
     float gx, gz, q;
 };
 
-// DEM sample (i, j) as the session holds it (f3d_raster.h raster_origin picks the same corner of the same record)
-F3D_HD float irradiation_height(const TerrainDev &T, uint32_t i, uint32_t j) {
-    const uint32_t cx = i < T.cell_w ? i : T.cell_w - 1u, cz = j < T.cell_h ? j : T.cell_h - 1u;
-    const LeafRec rec = T.leaves[tiled_index(cx, cz, T.tiles_x[0])];
-    return pick4((i - cx) | ((j - cz) << 1), rec.h00, rec.h10, rec.h01, rec.h11);
-}
-
 // DEM sample (i, j) of sample n of the region, and its lifted lattice point
 F3D_HD V3 irradiation_origin(const IrradiationParams &R, uint32_t n, uint32_t &i, uint32_t &j) {
-    const TerrainDev &T = R.frame.terrain;
-    const uint32_t r = n / R.cols, c = n - r * R.cols;
-    j = R.row0 + r;
-    i = R.col0 + c;
-    return V3{plane_at(T.origin_x, i, T.spacing_x), irradiation_height(T, i, j) + R.lift, plane_at(T.origin_z, j, T.spacing_z)};
+    return lattice_point(R.frame.terrain, R.row0, R.col0, R.cols, n, R.lift, i, j);
 }
 
 F3D_HD IrradiationSlope irradiation_slope(const IrradiationParams &R, uint32_t i, uint32_t j) {
@@ -66,8 +56,8 @@ F3D_HD IrradiationSlope irradiation_slope(const IrradiationParams &R, uint32_t i
     const uint32_t iW = i > 0u ? i - 1u : i, iE = i + 1u < w ? i + 1u : i, jN = j > 0u ? j - 1u : j, jS = j + 1u < h ? j + 1u : j;
     const float run_x = plane_at(T.origin_x, iE, T.spacing_x) - plane_at(T.origin_x, iW, T.spacing_x);
     const float run_z = plane_at(T.origin_z, jS, T.spacing_z) - plane_at(T.origin_z, jN, T.spacing_z);
-    const float gx = (irradiation_height(T, iE, j) - irradiation_height(T, iW, j)) / run_x;
-    const float gz = (irradiation_height(T, i, jS) - irradiation_height(T, i, jN)) / run_z;
+    const float gx = (lattice_height(T, iE, j) - lattice_height(T, iW, j)) / run_x;
+    const float gz = (lattice_height(T, i, jS) - lattice_height(T, i, jN)) / run_z;
     return IrradiationSlope{gx, gz, (gx * gx + gz * gz) + 1.0f};
 }
 

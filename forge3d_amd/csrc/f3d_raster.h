@@ -27,19 +27,14 @@
 #pragma once
 
 #include "f3d_query.h"
+#include "f3d_walk.h"
 
 namespace f3d {
 
 // the lifted lattice point of sample n of the region
 F3D_HD V3 raster_origin(const RasterParams &R, uint32_t n) {
-    const TerrainDev &T = R.frame.terrain;
-    const uint32_t r = n / R.cols, c = n - r * R.cols;
-    const uint32_t j = R.row0 + r, i = R.col0 + c;
-    // (DEM sample (i, j) is corner (i - cx, j - cz) of cell (cx, cz); the last row and column have no cell of their own)
-    const uint32_t cx = i < T.cell_w ? i : T.cell_w - 1u, cz = j < T.cell_h ? j : T.cell_h - 1u;
-    const LeafRec rec = T.leaves[tiled_index(cx, cz, T.tiles_x[0])];
-    const float h = pick4((i - cx) | ((j - cz) << 1), rec.h00, rec.h10, rec.h01, rec.h11);
-    return V3{plane_at(T.origin_x, i, T.spacing_x), h + R.lift, plane_at(T.origin_z, j, T.spacing_z)};
+    uint32_t i, j;
+    return lattice_point(R.frame.terrain, R.row0, R.col0, R.cols, n, R.lift, i, j);
 }
 
 // One lane, one target: is the target visible (the direction unblocked) from o?  Every lane of the wave that has a sample

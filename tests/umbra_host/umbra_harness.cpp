@@ -8,16 +8,10 @@
 // With -DUMBRA_DRIVER the file is a stand-alone program (its own main) over two synthetic DEMs, for a sanitizer build.
 #include "../emul/f3d_emul.cpp"
 #include "../emul/host_scene.h"
+#include "../emul/direct_levels.h"
 #include "../../forge3d_amd/csrc/f3d_umbra.h"
 
 namespace {
-struct DirectLevels {
-    void band_entry(const TerrainDev &T, uint32_t level, uint32_t &offset, uint32_t &shift) const {
-        offset = T.band_offset[level];
-        shift = T.band_shift[level];
-    }
-};
-
 // (directions null: one direction, `sun` -- what SESSION_SUN hands the kernel)
 void run_umbra(const TerrainDev &T, V3 sun, uint32_t flags, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols, uint32_t count,
                const float *directions, float *depth, float *deepest, float *samples, uint32_t cap, uint32_t block) {
