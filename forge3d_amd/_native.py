@@ -265,6 +265,33 @@ PAINT_POINTS, PAINT_LINES, PAINT_TRIANGLES = 0, 1, 2
 PAINT_MAX_PRIMITIVES = 1 << 24  # F3D_PAINT_MAX_PRIMITIVES
 
 
+class ContoursDesc(C.Structure):
+    """f3d_session_contours_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("level_count", C.c_uint32), ("reserved", C.c_uint32),
+        ("levels", C.c_void_p), ("segments", C.c_void_p), ("level_index", C.c_void_p),
+        ("capacity", C.c_uint64), ("total", C.c_void_p),
+    ]
+
+
+class PaintContoursDesc(C.Structure):
+    """f3d_session_paint_contours_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("level_count", C.c_uint32), ("reserved", C.c_uint32),
+        ("levels", C.c_void_p), ("total", C.c_void_p),
+        ("rgba", C.c_float * 4), ("half_width", C.c_float), ("opacity", C.c_float),
+        ("aim", ReaimDesc),
+    ]
+
+
+CONTOUR_DEVICE_POINTERS = 4
+CONTOUR_MAX_LEVELS = 65536  # F3D_CONTOUR_MAX_LEVELS
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -313,6 +340,8 @@ ABI = [
     ("f3d_session_draped", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
     ("f3d_session_paint", C.c_int, [C.c_void_p, _P(PaintDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_paint_stats", C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint64)]),
+    ("f3d_session_contours", C.c_int, [C.c_void_p, _P(ContoursDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_paint_contours", C.c_int, [C.c_void_p, _P(PaintContoursDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_void_p, C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_sky_blocks", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
@@ -383,7 +412,7 @@ KERNEL_FLAGS = [
     # default is now 1.1 % FASTER, 8 690 -> 8 785 Msamples/s in one call, same image; profiles/r04_variant_ab.log)
 ]
 HIP_SOURCES = ["f3d_kernels.hip", "f3d_host.hip", "f3d_denoise.hip", "f3d_smoke.hip", "f3d_smoke_sim.hip", "f3d_composite.hip", "f3d_lbvh.hip", "f3d_bvh_refit.hip", "f3d_retable.hip", "f3d_wavefront.hip",
-               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip"]
+               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip", "f3d_contour.hip"]
 
 
 def source_digest() -> str:

@@ -8,6 +8,100 @@ namespace {
 
 size_t paint_align(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
 
+// The canvas and the style of a call: everything of PaintParams but the records and the binning's storage.
+PaintParams paint_params(const f3d_session &s, uint32_t kind, float half_width, float opacity) {
+    const f3d_session::Drape &D = s.drape;
+    const TerrainDev &T = s.params.terrain;
+    PaintParams P{};
+    PaintCanvas &C = P.canvas;
+    C.texels = (uint2 *)((char *)D.buffer + sizeof(DrapeDev));
+    C.rows = D.rows;
+    C.cols = D.cols;
+    C.origin_x = T.origin_x, C.origin_z = T.origin_z, C.spacing_x = T.spacing_x, C.spacing_z = T.spacing_z;
+    C.scale_x = D.record.scale_x, C.offset_x = D.record.offset_x, C.scale_z = D.record.scale_z, C.offset_z = D.record.offset_z;
+    C.ramp = paint_ramp(T.spacing_x, C.scale_x, T.spacing_z, C.scale_z);
+    P.kind = kind;
+    P.half_width = half_width;
+    P.opacity = opacity;
+    return P;
+}
+
+// first buffer: records, counts, offsets, the run counter, the scan's storage -- known before anything runs.  Names them in P;
+// the records themselves are the caller's to put there, on the session stream (an upload: f3d_session_paint; a kernel:
+// f3d_session_paint_contours).
+struct PaintStorage {
+    void *scan_tmp;
+    size_t scan_bytes;
+};
+PaintStorage paint_records(f3d_session &s, PaintParams &P, uint32_t n) {
+    f3d_session::Paint &B = s.paint;
+    size_t scan_bytes = 0;
+    hip_check(paint_scan_bytes(n, &scan_bytes), "paint scan storage");
+    const size_t rec_bytes = paint_align((size_t)n * sizeof(PaintPrim)), word_bytes = paint_align(((size_t)n + 1u) * sizeof(uint64_t));
+    // (the old buffer may still be read by the previous call's kernels: see the second buffer in paint_run)
+    grow_scratch(s, B.prims, B.prim_bytes, rec_bytes + 2u * word_bytes + 256u + paint_align(scan_bytes), "paint",
+                 "the primitive records and the binning's counters bring", "paint primitives");
+    char *base = (char *)B.prims;
+    P.prims = (const PaintPrim *)base;
+    P.prim_count = n;
+    P.counts = (uint64_t *)(base + rec_bytes);
+    P.offsets = (const uint64_t *)(base + rec_bytes + word_bytes);
+    P.run_count = (uint32_t *)(base + rec_bytes + 2u * word_bytes);
+    return {base + rec_bytes + 2u * word_bytes + 256u, scan_bytes};
+}
+
+// The records are on the device (or on their way, on the session stream): count, bin, paint, with the timing marks.
+void paint_run(f3d_session &s, PaintParams &P, const PaintStorage &at) {
+    f3d_session::Paint &B = s.paint;
+    const PaintCanvas &C = P.canvas;
+    const uint32_t n = P.prim_count, tiles = paint_tiles_x(C) * paint_tiles_z(C);
+    void *scan_tmp = at.scan_tmp;
+    const size_t scan_bytes = at.scan_bytes;
+    for (hipEvent_t &e : B.mark)
+        if (!e) hip_check(hipEventCreate(&e), "paint timing event");
+    B.timed = false;
+    B.last[0] = n, B.last[1] = B.last[2] = 0u;
+    hip_check(hipEventRecord(B.mark[0], s.stream), "paint timing event");
+    hip_check(launch_paint_count(P, scan_tmp, scan_bytes, s.stream), "paint count kernels");
+    hip_check(hipEventRecord(B.mark[1], s.stream), "paint timing event");
+    uint64_t total = 0u;
+    hip_check(hipMemcpyAsync(&total, P.offsets + n, sizeof total, hipMemcpyDeviceToHost, s.stream), "paint key count");
+    hip_check(hipStreamSynchronize(s.stream), "paint key count");
+
+    if (total > 0u) {
+        // second buffer, sized exactly now: keys, sorted keys, the run list, the sort's storage
+        if (total > 0xFFFF0000ull)
+            fail(F3D_STATUS_RENDER, "paint exceeds the memory budget: %llu (tile, primitive) pairs cannot be listed", (unsigned long long)total);
+        P.key_count = (uint32_t)total;
+        size_t sort_bytes = 0;
+        hip_check(paint_sort_bytes(P.key_count, tiles, &sort_bytes), "paint sort storage");
+        const size_t key_bytes = paint_align((size_t)total * sizeof(uint64_t)), run_bytes = paint_align((size_t)std::min<uint64_t>(total, tiles) * sizeof(uint32_t));
+        // (a refusal here leaves the first buffer as it has just grown -- gpu_resource_bytes may have risen -- and everything a
+        // render or fingerprint reads as it was.  grow_scratch gives the old buffer back at once although the previous call's k_paint
+        // may still read it: Ledger::free ends in the pool's device-wide wait or in hipFree, which waits too; a free path that did
+        // not would have to wait for the session stream here first)
+        grow_scratch(s, B.keys, B.key_bytes, 2u * key_bytes + run_bytes + paint_align(sort_bytes), "paint",
+                     "the (tile, primitive) keys and the storage of their sort bring", "paint keys");
+        char *kb = (char *)B.keys;
+        P.keys = (uint64_t *)kb;
+        P.sorted = (const uint64_t *)(kb + key_bytes);
+        P.runs = (uint32_t *)(kb + 2u * key_bytes);
+        hip_check(hipEventRecord(B.mark[2], s.stream), "paint timing event");  // (behind the wait for the key count)
+        hip_check(launch_paint_bin(P, tiles, kb + 2u * key_bytes + run_bytes, sort_bytes, s.stream), "paint binning kernels");
+        hip_check(hipEventRecord(B.mark[3], s.stream), "paint timing event");
+        uint32_t runs = 0u;
+        hip_check(hipMemcpyAsync(&runs, P.run_count, sizeof runs, hipMemcpyDeviceToHost, s.stream), "paint tile count");
+        hip_check(hipStreamSynchronize(s.stream), "paint tile count");
+        if (runs == 0u || runs > tiles) fail(F3D_STATUS_DEVICE, "paint binning listed %u tiles of %u", runs, tiles);
+        join_bands(s);  // (frames of bands on their own streams still sample the canvas)
+        hip_check(hipEventRecord(B.mark[4], s.stream), "paint timing event");  // (behind the wait for the tile count)
+        hip_check(launch_paint(P, runs, s.stream), "paint kernel");
+        hip_check(hipEventRecord(B.mark[5], s.stream), "paint timing event");
+        B.last[1] = total, B.last[2] = runs;
+        B.timed = true;
+    }
+}
+
 void session_paint(f3d_session &s, const f3d_session_paint_desc &q) {
     check_struct_size(q, "f3d_session_paint_desc");
     Update u(s, q.aim.arm, &q.aim, "painted");
@@ -63,79 +157,10 @@ void session_paint(f3d_session &s, const f3d_session_paint_desc &q) {
         p.feature = run;
     }
 
-    const TerrainDev &T = s.params.terrain;
-    PaintParams P{};
-    PaintCanvas &C = P.canvas;
-    C.texels = (uint2 *)((char *)D.buffer + sizeof(DrapeDev));
-    C.rows = D.rows;
-    C.cols = D.cols;
-    C.origin_x = T.origin_x, C.origin_z = T.origin_z, C.spacing_x = T.spacing_x, C.spacing_z = T.spacing_z;
-    C.scale_x = D.record.scale_x, C.offset_x = D.record.offset_x, C.scale_z = D.record.scale_z, C.offset_z = D.record.offset_z;
-    C.ramp = paint_ramp(T.spacing_x, C.scale_x, T.spacing_z, C.scale_z);
-    P.prim_count = n;
-    P.kind = q.primitive;
-    P.half_width = q.primitive == F3D_PAINT_TRIANGLES ? 0.0f : q.half_width;
-    P.opacity = q.opacity;
-    const uint32_t tiles = paint_tiles_x(C) * paint_tiles_z(C);
-
-    // first buffer: records, counts, offsets, the run counter, the scan's storage -- known before anything runs
-    f3d_session::Paint &B = s.paint;
-    size_t scan_bytes = 0;
-    hip_check(paint_scan_bytes(n, &scan_bytes), "paint scan storage");
-    const size_t rec_bytes = paint_align((size_t)n * sizeof(PaintPrim)), word_bytes = paint_align(((size_t)n + 1u) * sizeof(uint64_t));
-    // (the old buffer may still be read by the previous call's kernels: see the second buffer below)
-    grow_scratch(s, B.prims, B.prim_bytes, rec_bytes + 2u * word_bytes + 256u + paint_align(scan_bytes), "paint",
-                 "the primitive records and the binning's counters bring", "paint primitives");
-    char *base = (char *)B.prims;
-    P.prims = (const PaintPrim *)base;
-    P.counts = (uint64_t *)(base + rec_bytes);
-    P.offsets = (const uint64_t *)(base + rec_bytes + word_bytes);
-    P.run_count = (uint32_t *)(base + rec_bytes + 2u * word_bytes);
-    void *scan_tmp = base + rec_bytes + 2u * word_bytes + 256u;
-    upload_staged(B.prims, recs.data(), (size_t)n * sizeof(PaintPrim), s.stream, true);
-    for (hipEvent_t &e : B.mark)
-        if (!e) hip_check(hipEventCreate(&e), "paint timing event");
-    B.timed = false;
-    B.last[0] = n, B.last[1] = B.last[2] = 0u;
-    hip_check(hipEventRecord(B.mark[0], s.stream), "paint timing event");
-    hip_check(launch_paint_count(P, scan_tmp, scan_bytes, s.stream), "paint count kernels");
-    hip_check(hipEventRecord(B.mark[1], s.stream), "paint timing event");
-    uint64_t total = 0u;
-    hip_check(hipMemcpyAsync(&total, P.offsets + n, sizeof total, hipMemcpyDeviceToHost, s.stream), "paint key count");
-    hip_check(hipStreamSynchronize(s.stream), "paint key count");
-
-    if (total > 0u) {
-        // second buffer, sized exactly now: keys, sorted keys, the run list, the sort's storage
-        if (total > 0xFFFF0000ull)
-            fail(F3D_STATUS_RENDER, "paint exceeds the memory budget: %llu (tile, primitive) pairs cannot be listed", (unsigned long long)total);
-        P.key_count = (uint32_t)total;
-        size_t sort_bytes = 0;
-        hip_check(paint_sort_bytes(P.key_count, tiles, &sort_bytes), "paint sort storage");
-        const size_t key_bytes = paint_align((size_t)total * sizeof(uint64_t)), run_bytes = paint_align((size_t)std::min<uint64_t>(total, tiles) * sizeof(uint32_t));
-        // (a refusal here leaves the first buffer as it has just grown -- gpu_resource_bytes may have risen -- and everything a
-        // render or fingerprint reads as it was.  grow_scratch gives the old buffer back at once although the previous call's k_paint
-        // may still read it: Ledger::free ends in the pool's device-wide wait or in hipFree, which waits too; a free path that did
-        // not would have to wait for the session stream here first)
-        grow_scratch(s, B.keys, B.key_bytes, 2u * key_bytes + run_bytes + paint_align(sort_bytes), "paint",
-                     "the (tile, primitive) keys and the storage of their sort bring", "paint keys");
-        char *kb = (char *)B.keys;
-        P.keys = (uint64_t *)kb;
-        P.sorted = (const uint64_t *)(kb + key_bytes);
-        P.runs = (uint32_t *)(kb + 2u * key_bytes);
-        hip_check(hipEventRecord(B.mark[2], s.stream), "paint timing event");  // (behind the wait for the key count)
-        hip_check(launch_paint_bin(P, tiles, kb + 2u * key_bytes + run_bytes, sort_bytes, s.stream), "paint binning kernels");
-        hip_check(hipEventRecord(B.mark[3], s.stream), "paint timing event");
-        uint32_t runs = 0u;
-        hip_check(hipMemcpyAsync(&runs, P.run_count, sizeof runs, hipMemcpyDeviceToHost, s.stream), "paint tile count");
-        hip_check(hipStreamSynchronize(s.stream), "paint tile count");
-        if (runs == 0u || runs > tiles) fail(F3D_STATUS_DEVICE, "paint binning listed %u tiles of %u", runs, tiles);
-        join_bands(s);  // (frames of bands on their own streams still sample the canvas)
-        hip_check(hipEventRecord(B.mark[4], s.stream), "paint timing event");  // (behind the wait for the tile count)
-        hip_check(launch_paint(P, runs, s.stream), "paint kernel");
-        hip_check(hipEventRecord(B.mark[5], s.stream), "paint timing event");
-        B.last[1] = total, B.last[2] = runs;
-        B.timed = true;
-    }
+    PaintParams P = paint_params(s, q.primitive, q.primitive == F3D_PAINT_TRIANGLES ? 0.0f : q.half_width, q.opacity);
+    const PaintStorage at = paint_records(s, P, n);
+    upload_staged(s.paint.prims, recs.data(), (size_t)n * sizeof(PaintPrim), s.stream, true);
+    paint_run(s, P, at);
     u.apply();
 }
 

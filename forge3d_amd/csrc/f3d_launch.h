@@ -56,6 +56,13 @@ hipError_t paint_sort_bytes(uint32_t key_count, uint32_t tiles, size_t *bytes);
 hipError_t launch_paint_count(const PaintParams &p, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
 hipError_t launch_paint_bin(const PaintParams &p, uint32_t tiles, void *sort_tmp, size_t sort_bytes, hipStream_t stream);
 hipError_t launch_paint(const PaintParams &p, uint32_t run_count, hipStream_t stream);
+// contour lines of a session's terrain (f3d_contour.h, f3d_contour.hip): the temporary storage of the scan over blocks + 1
+// totals; count pass + scan (P.totals, P.offsets: nbx * nbz + 1 words each, offsets[nbx * nbz] = the number of segments); the
+// emit pass into P.segments / P.level_index or P.prims, the first P.capacity records
+struct ContourParams;
+hipError_t contour_scan_bytes(uint32_t blocks, size_t *bytes);
+hipError_t launch_contour_count(const ContourParams &p, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
+hipError_t launch_contour_emit(const ContourParams &p, hipStream_t stream);
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream);
 hipError_t launch_query(const QueryParams &p, hipStream_t stream);  // ray queries on a live session (f3d_query.h), 64 rays a workgroup
 hipError_t launch_raster(const RasterParams &p, hipStream_t stream);  // DEM visibility rasters (f3d_raster.h), 64 consecutive samples a workgroup

@@ -121,6 +121,7 @@ class TerrainSession:
         dem = np.asarray(heightmap, dtype=np.float32)
         self._exaggeration = float(desc.exaggeration)
         self._terrain_top = float(dem.max()) * self._exaggeration
+        self._terrain_bottom = float(dem.min()) * self._exaggeration  # (a lower bound, kept like the upper one: contour_levels())
         self._mesh_top = float(np.asarray(mesh_vertices, dtype=np.float32)[:, 1].max()) if mesh_vertices is not None else None
         self.dem_shape = (int(desc.dem_height), int(desc.dem_width))
         self.row_begin = int(row_begin)
@@ -238,8 +239,10 @@ class TerrainSession:
         if exaggeration is not None:  # (accepted only with the whole DEM: the bound is exact again)
             self._exaggeration = float(np.float32(exaggeration))
             self._terrain_top = float(block.max()) * self._exaggeration
+            self._terrain_bottom = float(block.min()) * self._exaggeration
         else:
             self._terrain_top = max(self._terrain_top, float(block.max()) * self._exaggeration)
+            self._terrain_bottom = min(self._terrain_bottom, float(block.min()) * self._exaggeration)
 
     # -- drape: an image laid over the terrain, per-texel albedo -----------------------------------
     DRAPE_FILTERS = {"nearest": _native.DRAPE_NEAREST, "bilinear": _native.DRAPE_BILINEAR}
@@ -441,6 +444,179 @@ class TerrainSession:
         if not self._lib.f3d_session_paint_stats(self._handle, ms, counts):
             return None
         return {"count_ms": ms[0], "bin_ms": ms[1], "paint_ms": ms[2], "primitives": int(counts[0]), "keys": int(counts[1]), "tiles": int(counts[2])}
+
+    # -- contour lines: extracted, and painted into the drape, on the GPU -------------------------------
+    def contour_levels(self, interval, base=0.0):
+        """The levels ``base + k * interval`` (float32, ascending) that can cross the session's terrain: over bounds of its
+        height range -- heights times the exaggeration, the y of ground() -- kept up by reterrain().  A bound only has to
+        contain the range: a level outside it costs a bisection step and draws nothing."""
+        interval, base = float(interval), float(base)
+        if not np.isfinite(interval) or interval <= 0.0 or not np.isfinite(base):
+            raise ValueError(f"interval must be finite and > 0 and base finite, got interval={interval}, base={base}")
+        lo, hi = sorted((self._terrain_bottom, self._terrain_top))
+        k0, k1 = int(np.floor((lo - base) / interval)), int(np.ceil((hi - base) / interval))
+        if k1 - k0 + 1 > _native.CONTOUR_MAX_LEVELS:
+            raise ValueError(f"interval {interval} gives {k1 - k0 + 1} levels over heights [{lo}, {hi}]: a call takes at most {_native.CONTOUR_MAX_LEVELS}")
+        levels = np.unique((base + np.arange(k0, k1 + 1, dtype=np.float64) * interval).astype(np.float32))
+        return levels
+
+    def _contour_levels(self, levels, interval, base):
+        if (levels is None) == (interval is None):
+            raise ValueError("give either levels or interval=")
+        if levels is None:
+            return self.contour_levels(interval, base)
+        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.float32).reshape(-1))
+        if lv.size == 0:
+            raise ValueError("levels is empty")
+        if lv.size > _native.CONTOUR_MAX_LEVELS:
+            raise ValueError(f"a contour call takes at most {_native.CONTOUR_MAX_LEVELS} levels, got {lv.size}")
+        if not np.all(np.isfinite(lv)) or not np.all(lv[1:] > lv[:-1]):
+            raise ValueError("levels must be finite and strictly ascending (as float32)")
+        return lv
+
+    def _cell_region(self, region):
+        """``(row0, col0, rows, cols)`` in CELLS, default the whole cell grid.  Whether it lies inside is the library's check."""
+        dem_h, dem_w = self.dem_shape
+        row0, col0, rows, cols = (0, 0, dem_h - 1, dem_w - 1) if region is None else (int(v) for v in region)
+        if min(row0, col0, rows, cols) < 0:
+            raise ValueError(f"region=(row0, col0, rows, cols) must not be negative, got {tuple(region)}")
+        return row0, col0, rows, cols
+
+    def contours(self, levels=None, *, interval=None, base=0.0, region=None, chain=False, out=None):
+        """The contour lines of the terrain this session renders, extracted on the GPU from its own tables (f3d_session_contours):
+        marching squares over the cells of ``region`` (``(row0, col0, rows, cols)`` in cells, default all) at ``levels`` --
+        finite, strictly ascending float32, in the unit of ground()'s y (heights times the exaggeration) -- or at
+        ``base + k * interval`` (contour_levels()).  They stay right after reterrain().
+        Returns ``{"segments": (N, 4) float32 (ax, az, bx, bz) in world x-z, "level_index": (N,) uint32 into "levels",
+        "levels": the float32 levels, "total": N}``, the segments in block order (8 x 8 blocks of cells row-major, cells row-major
+        in a block, levels ascending in a cell).  Ends of neighbouring segments are bit-identical: ``chain=True`` adds
+        ``"polylines"`` (chain_contours()).  A level through a DEM sample gives zero-length segments.
+        ``out=(segments, level_index)``, torch tensors on the session's device of shape (C, 4) float32 and (C,) int32
+        (``level_index`` may be None), takes the device form: the first ``min(N, C)`` records are written there in one call,
+        the values returned are views of them and ``"total"`` is N."""
+        lv = self._contour_levels(levels, interval, base)
+        row0, col0, rows, cols = self._cell_region(region)
+        if out is not None and chain:
+            raise ValueError("chain=True joins segments on the host: it needs the host form (out=None)")
+        total = C.c_uint64(0)
+        q = _native.ContoursDesc()
+        q.struct_size = C.sizeof(_native.ContoursDesc)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.levels, q.level_count = lv.ctypes.data, lv.size
+        q.total = C.addressof(total)
+        entry = self._lib.f3d_session_contours
+        if out is not None:
+            seg, idx = out
+            if not _is_tensor(seg) or not seg.is_cuda or seg.ndim != 2 or seg.shape[1] != 4 or not seg.is_contiguous() or str(seg.dtype) != "torch.float32":
+                raise ValueError("out=(segments, level_index): segments must be a contiguous float32 tensor (C, 4) on the session's device")
+            if idx is not None and (not _is_tensor(idx) or not idx.is_cuda or idx.ndim != 1 or idx.shape[0] != seg.shape[0] or
+                                    not idx.is_contiguous() or str(idx.dtype) != "torch.int32"):
+                raise ValueError("out=(segments, level_index): level_index must be a contiguous int32 tensor (C,) on the session's device, or None")
+            q.flags = _native.CONTOUR_DEVICE_POINTERS
+            q.capacity = int(seg.shape[0])
+            q.segments = seg.data_ptr() if seg.shape[0] else None
+            q.level_index = idx.data_ptr() if idx is not None and seg.shape[0] else None
+            self._check(entry(self._handle, C.byref(q), self._err, len(self._err)))
+            n = min(int(total.value), int(seg.shape[0]))
+            return {"segments": seg[:n], "level_index": None if idx is None else idx[:n], "levels": lv, "total": int(total.value)}
+        self._check(entry(self._handle, C.byref(q), self._err, len(self._err)))  # (null outputs: the total)
+        n = int(total.value)
+        seg, idx = np.zeros((n, 4), np.float32), np.zeros(n, np.uint32)
+        if n:
+            q.capacity = n
+            q.segments, q.level_index = seg.ctypes.data, idx.ctypes.data
+            self._check(entry(self._handle, C.byref(q), self._err, len(self._err)))
+        got = {"segments": seg, "level_index": idx, "levels": lv, "total": n}
+        if chain:
+            got["polylines"] = self.chain_contours(seg, idx)
+        return got
+
+    @staticmethod
+    def chain_contours(segments, level_index):
+        """Segments of contours() joined into polylines, on the host: ``[{"level_index": k, "closed": bool, "points": (M, 2)
+        float32}, ...]`` in order of level, then of the first segment used.  Two segment ends are joined when they belong to
+        one level and are bit-identical -- which neighbouring cells' crossings are (a crossing belongs to its lattice edge).  A
+        point where exactly two ends meet continues the chain; where more meet (a level through a DEM sample: crossings
+        coincide in fours and sixes) or one ends (the region's border), chains end.  A closed loop repeats its first point
+        at the end.  Zero-length segments make no chain of their own, but their ends count at the point where they lie."""
+        seg = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
+        idx = np.asarray(level_index).reshape(-1)
+        if idx.shape[0] != seg.shape[0]:
+            raise ValueError(f"{seg.shape[0]} segments but {idx.shape[0]} level indices")
+        out = []
+        seg = np.where(seg == 0.0, np.float32(0.0), seg)  # (-0 and +0 are one point)
+        keys = seg.view(np.uint32).reshape(-1, 2, 2).astype(np.uint64)
+        keys = (keys[:, :, 0] << np.uint64(32)) | keys[:, :, 1]  # (N, 2): an end's bits
+        for level in np.unique(idx):
+            rows = np.nonzero((idx == level) & (keys[:, 0] != keys[:, 1]))[0]
+            ends = {}
+            for r in np.nonzero(idx == level)[0]:  # (a zero-length segment's two ends count where they lie: more than two meet there)
+                for e in (0, 1):
+                    ends.setdefault(int(keys[r, e]), []).append((int(r), e))
+            used = set()
+
+            def walk(r, e):
+                """From segment r entered at end e: the points after its first, until a chain end or a return to `r`."""
+                pts, first = [], r
+                while True:
+                    used.add(r)
+                    pts.append(seg[r, 2 * (1 - e):2 * (1 - e) + 2])
+                    meet = ends[int(keys[r, 1 - e])]
+                    if len(meet) != 2:
+                        return pts, False
+                    (r2, e2) = meet[0] if meet[1] == (r, 1 - e) else meet[1]
+                    if r2 == first:
+                        return pts, True
+                    if r2 in used:
+                        return pts, False
+                    r, e = r2, e2
+
+            # open chains first, from their ends (points where not exactly two ends meet), then the loops that remain
+            for r in rows:
+                for e in (0, 1):
+                    if int(r) not in used and len(ends[int(keys[r, e])]) != 2:
+                        pts, _ = walk(int(r), e)
+                        out.append({"level_index": int(level), "closed": False, "points": np.array([seg[r, 2 * e:2 * e + 2]] + pts, np.float32)})
+            for r in rows:
+                if int(r) not in used:
+                    pts, closed = walk(int(r), 0)
+                    out.append({"level_index": int(level), "closed": bool(closed), "points": np.array([seg[r, 0:2]] + pts, np.float32)})
+        return out
+
+    def paint_contours(self, levels=None, *, interval=None, base=0.0, rgba=(0.0, 0.0, 0.0, 0.8), width=1.0, opacity=1.0, region=None,
+                       camera=None, **rearmable):
+        """paint() of the terrain's own contour lines, without the segments leaving the GPU (f3d_session_paint_contours): the
+        segments contours() returns for ``levels`` (or ``interval`` / ``base``) and ``region`` are emitted into the session's
+        paint buffer and rasterised into the drape as ``paint(segments, rgba, primitive="lines", width=width, opacity=opacity)``
+        paints them, bit for bit.  One call is one stroke style and one feature (joints blend once); index contours are a
+        second call with every n-th level.  ``rgba``: one linear colour with alpha (three numbers: alpha 1).  ``camera`` and the
+        other values as reaim() takes them; the render restarts at frame 0; a refused value leaves the session and the canvas
+        as they were.  Returns the number of segments painted."""
+        self._known("paint_contours", rearmable)
+        lv = self._contour_levels(levels, interval, base)
+        row0, col0, rows, cols = self._cell_region(region)
+        col = np.asarray(rgba, dtype=np.float32).reshape(-1)
+        if col.shape[0] not in (3, 4):
+            raise ValueError(f"rgba must be one colour of 3 or 4 numbers, got {np.shape(rgba)}")
+        if col.shape[0] == 3:
+            col = np.concatenate([col, np.ones(1, np.float32)])
+        width, opacity = float(width), float(opacity)
+        if not np.isfinite(width) or width < 0.0:
+            raise ValueError(f"width must be finite and >= 0 metres, got {width}")
+        if not 0.0 <= opacity <= 1.0:
+            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+        total = C.c_uint64(0)
+        q = _native.PaintContoursDesc()
+        q.struct_size = C.sizeof(_native.PaintContoursDesc)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.levels, q.level_count = lv.ctypes.data, lv.size
+        q.total = C.addressof(total)
+        q.rgba = (C.c_float * 4)(*(float(v) for v in col))
+        q.half_width = np.float32(width) * np.float32(0.5)
+        q.opacity = opacity
+        q.aim = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_paint_contours, q, q.aim.arm, camera)  # (lv lives until here)
+        return int(total.value)
 
     def drape_image(self, region=None):
         """The session's drape as ``(rows, cols, 3)`` float32 linear RGB -- the values its binary16 texels hold -- after

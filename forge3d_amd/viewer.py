@@ -47,6 +47,7 @@ class ViewerHandle(OfflineTerrainViewer):
         self._open = True
         self._overlay = None
         self._vector_layers = {}
+        self._contours = None
         self._vector_next_id = 1
         self._vector_canvas = None
 
@@ -289,10 +290,40 @@ class ViewerHandle(OfflineTerrainViewer):
         k, cap = self.VECTOR_CANVAS_TEXELS_PER_CELL, self.VECTOR_CANVAS_MAX_SIDE
         return (min(k * max(dem_shape[0] - 1, 1), cap), min(k * max(dem_shape[1] - 1, 1), cap))
 
+    def enable_contours(self, interval: float, *, base: float = 0.0, width: float = 1.5, rgba=(0.0, 0.0, 0.0, 0.8), index_every: int = 0,
+                        index_width: float = 3.0) -> None:
+        """Contour lines of the terrain as it is rendered (heights times the z scale), every ``interval`` from ``base``, painted
+        on the GPU from the session's own tables (TerrainSession.paint_contours) after the overlay image and before the vector
+        layers.  ``width`` and ``index_width`` are stroke widths in canvas texels, like a vector layer's ``line_width``;
+        ``index_every`` = n > 0 paints every n-th level (counted from ``base``) a second time ``index_width`` wide.  ``rgba``:
+        linear colour and alpha, default the reference overlay's."""
+        interval, base, width, index_width = float(interval), float(base), float(width), float(index_width)
+        if not np.isfinite(interval) or interval <= 0.0 or not np.isfinite(base):
+            raise ViewerError(f"contour interval must be finite and > 0 and base finite, got interval={interval}, base={base}")
+        if not (np.isfinite(width) and width >= 0.0 and np.isfinite(index_width) and index_width >= 0.0):
+            raise ViewerError(f"contour widths must be finite and >= 0 texels, got {width} and {index_width}")
+        colour = np.asarray(rgba, np.float32).reshape(-1)
+        if colour.shape[0] not in (3, 4) or not np.all((colour >= 0.0) & (colour <= 1.0)):
+            raise ViewerError("contour rgba must be 3 or 4 numbers in [0, 1]")
+        if int(index_every) < 0:
+            raise ViewerError(f"index_every must be >= 0, got {index_every}")
+        self._contours = {"interval": interval, "base": base, "width": width, "rgba": tuple(float(c) for c in colour),
+                          "index_every": int(index_every), "index_width": index_width}
+        self._revision += 1
+
+    def disable_contours(self) -> None:
+        self._contours = None
+        self._revision += 1
+
+    def _painted(self) -> bool:
+        """Does the scene need a painted canvas: contour lines or vector layers?"""
+        return self._contours is not None or bool(self.vector_layers())
+
     def _paint_layers(self, s, keywords) -> None:
-        """Drape ``s`` with the constant canvas unless an overlay image is there already, then paint the layers."""
+        """Drape ``s`` with the constant canvas unless an overlay image is there already, then paint the contour lines and,
+        over them, the layers."""
         layers = self.vector_layers()
-        if not layers:
+        if not self._painted():
             return
         if not s.draped:
             rows, cols = self.vector_canvas_shape(s.dem_shape)
@@ -303,6 +334,15 @@ class ViewerHandle(OfflineTerrainViewer):
                         if self._overlay is not None else s.drape_registration(info["rows"], info["cols"], "area"))
         spacing = keywords.get("spacing", (1.0, 1.0))
         texel = max(abs(float(spacing[0]) / float(sx)), abs(float(spacing[1]) / float(sz)))  # one canvas texel in metres
+        c = self._contours
+        if c is not None:
+            levels = s.contour_levels(c["interval"], c["base"])
+            s.paint_contours(levels, rgba=c["rgba"], width=c["width"] * texel)
+            if c["index_every"] > 0:
+                k = np.rint((levels.astype(np.float64) - c["base"]) / c["interval"]).astype(np.int64)
+                index = levels[k % c["index_every"] == 0]
+                if index.size:
+                    s.paint_contours(index, rgba=c["rgba"], width=c["index_width"] * texel)
         for layer in layers:
             s.paint(layer["xz"], layer["rgba"], layer["indices"], primitive=layer["primitive"], width=layer["texels"] * texel,
                     opacity=layer["opacity"], features=layer["features"])
@@ -310,7 +350,7 @@ class ViewerHandle(OfflineTerrainViewer):
     def render(self, width: Optional[int] = None, height: Optional[int] = None) -> dict:
         """OfflineTerrainViewer.render; with an overlay or vector layers loaded, the same loop on a session draped with them."""
         overlay = getattr(self, "_overlay", None)
-        if overlay is None and not self.vector_layers():
+        if overlay is None and not self._painted():
             return super().render(width, height)
         dem, w, h, camera, keywords = self._call(width, height)
         with self._draped_session(dem, w, h, camera, keywords) as s:
@@ -350,7 +390,7 @@ class ViewerHandle(OfflineTerrainViewer):
 
         out = Path(output_dir)
         out.mkdir(parents=True, exist_ok=True)
-        if self._overlay is not None or self.vector_layers():  # (a draped scene: ONE session draped and painted, re-aimed per key)
+        if self._overlay is not None or self._painted():  # (a draped scene: ONE session draped and painted, re-aimed per key)
             session = None
             try:
                 for i, key in enumerate(animation):

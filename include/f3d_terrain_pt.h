@@ -41,7 +41,9 @@ extern "C" {
  *   6  round 6: + f3d_smoke_seq_* (a smoke sequence behind a handle: its streams, its ordering, its scratch).  The handle-less
  *               smoke entry points are synchronous again, as in ABI 4, unless the thread has called f3d_smoke_set_stream --
  *               which, with f3d_smoke_wait_fields_read, stays for this one revision as a shim over the thread's default
- *               context.  No struct changed: a caller built against version 3, 4 or 5 keeps working. */
+ *               context.  No struct changed: a caller built against version 3, 4 or 5 keeps working.
+ *      since:   entry points with structs of their own are added without a bump and detected by their symbol (the session
+ *               updates, queries, rasters, drape and paint; f3d_session_contours, f3d_session_paint_contours) */
 #define F3D_ABI_VERSION 6u
 #define F3D_STATUS_OK 0
 #define F3D_STATUS_VALUE 1
@@ -825,6 +827,66 @@ int f3d_session_paint(f3d_session *session, const f3d_session_paint_desc *desc, 
  * list, paint kernel} from events on the session stream (waits for them); counts = {primitives, (tile, primitive) keys, tiles
  * painted}.  Either may be NULL.  Returns 1, or 0 when the session has not painted. */
 int f3d_session_paint_stats(f3d_session *session, double ms[3], uint64_t counts[3]);
+/* ---- contour lines: extracted, and painted into the drape, on the device ---------------------------------------------------
+ * Marching squares over the cells of the session's terrain, as the leaf table holds it: heights are f32(h * exaggeration), the y
+ * that a ground query returns, and `levels` are in that unit -- finite, strictly ascending, at most F3D_CONTOUR_MAX_LEVELS.  The
+ * rule is the opening comment of csrc/f3d_contour.h (f32, one rounding per operation): the case of a cell is the sum of its
+ * corners' bits (h >= level; h00 1, h10 2, h01 4, h11 8), the segment table and the fixed pairing of the two saddles are the
+ * reference's contour_extract's, and a crossing belongs to its lattice EDGE -- the two cells sharing an edge compute the same
+ * bits, so the ends of neighbouring segments are bit-identical and can be joined by comparing bits; a level through a sample
+ * gives zero-length segments, which are emitted.  The region is a region of CELLS {row0, col0, rows, cols} of the
+ * (dem_height - 1) x (dem_width - 1) grid.  Records come in "block order": blocks of 8 x 8 cells aligned to the cell grid,
+ * row-major over blocks, cells row-major in a block, levels ascending in a cell, a case's segments in table order.
+ *
+ * f3d_session_contours is a query (ordered on the session stream behind everything enqueued; the render goes on): it writes the
+ * first min(*total, capacity) records -- segments: 4 f32 (ax, az, bx, bz) in world x-z; level_index: the level's index in
+ * `levels` -- and always *total, so a call with capacity 0 sizes the next.  levels and total are host memory; with
+ * DEVICE_POINTERS segments (16-byte aligned) and level_index are device memory.  There is no NO_WAIT: the total crosses the bus.
+ * Refused with status 1, in this order: the struct size; unknown flags; reserved != 0; an empty region; a region that leaves
+ * the cell grid; NULL levels or level_count 0; more than F3D_CONTOUR_MAX_LEVELS; a non-finite level or levels not strictly
+ * ascending; NULL total; capacity > 0 with NULL segments (segments or level_index with capacity 0 is legal; level_index may be
+ * NULL); with DEVICE_POINTERS, segments not 16-byte aligned.  Status 2: the scratch (16 bytes a block, the levels, in the host
+ * form the min(*total, capacity) records written -- not the capacity) does not fit memory_budget_bytes.  Both entry points answer
+ * status 4 before any other check in a process without a HIP device.
+ *
+ * f3d_session_paint_contours is an update like f3d_session_paint (the render restarts at frame 0, aim as there): the segments
+ * are emitted on the device straight into the session's paint buffer -- as `lines` of one feature with one colour, the bits
+ * f3d_session_paint builds for the same segments -- and rasterised by the same kernels; *total is the number painted (0: the
+ * drape keeps its bits).  Refused, in this order, the session and its drape unchanged: the struct size (its own, aim's, the
+ * re-arm's), peer halos, then as above through NULL total (status 1); a session without a drape; half_width negative or
+ * non-finite; opacity outside [0, 1]; rgba outside [0, 1]; a corner of the region more than 65536 texels of the drape from the
+ * terrain's centre (status 3, as f3d_session_paint's reach); the re-arm's own refusals; and, after the count pass, more than
+ * F3D_PAINT_MAX_PRIMITIVES segments (status 1) or buffers beyond memory_budget_bytes (status 2).
+ * No ABI version bump: detected by the symbols f3d_session_contours and f3d_session_paint_contours. */
+#define F3D_CONTOUR_DEVICE_POINTERS 4u
+#define F3D_CONTOUR_MAX_LEVELS 65536u
+typedef struct f3d_session_contours_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_contours_desc) of the caller's header */
+    uint32_t flags;              /* F3D_CONTOUR_DEVICE_POINTERS */
+    uint32_t row0, col0, rows, cols; /* the region, in cells */
+    uint32_t level_count;
+    uint32_t reserved;           /* 0 */
+    const float *levels;         /* level_count f32, host memory, read during the call only */
+    float *segments;             /* capacity x 4 f32, or NULL */
+    uint32_t *level_index;       /* capacity u32, or NULL */
+    uint64_t capacity;           /* records the outputs hold */
+    uint64_t *total;             /* host memory: the number of segments of the region */
+} f3d_session_contours_desc;
+int f3d_session_contours(f3d_session *session, const f3d_session_contours_desc *desc, char *err, size_t errlen);
+typedef struct f3d_session_paint_contours_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_paint_contours_desc) of the caller's header */
+    uint32_t flags;              /* none defined: 0 */
+    uint32_t row0, col0, rows, cols; /* the region, in cells */
+    uint32_t level_count;
+    uint32_t reserved;           /* 0 */
+    const float *levels;         /* level_count f32, host memory, read during the call only */
+    uint64_t *total;             /* host memory: the number of segments painted */
+    float rgba[4];               /* [0, 1]: linear RGB reflectance and alpha of every segment */
+    float half_width;            /* metres: half the stroke width */
+    float opacity;               /* [0, 1] */
+    f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
+} f3d_session_paint_contours_desc;
+int f3d_session_paint_contours(f3d_session *session, const f3d_session_paint_contours_desc *desc, char *err, size_t errlen);
 /* The drape's texels as f32 RGB in host memory, after everything enqueued on the session: region = {row0, col0, rows, cols} (NULL:
  * the whole drape), rgb_out = rows x cols x 3 f32.  What a composed map is saved with.  Status 1: no drape, a region that leaves it. */
 int f3d_session_drape_read(f3d_session *session, const uint32_t region[4], float *rgb_out, char *err, size_t errlen);
