@@ -5,9 +5,7 @@
 // THE CONTRACT.  Terrain only: a session with a mesh answers for the ground, as the horizon raster does.  All arithmetic is
 // f32, one rounding per written operation (f3d_math.h), so the host build (tests/clearance_host) and the device return the
 // same bits.
-// Sample n = r * cols + c of the region is DEM sample (j = row0 + r, i = col0 + c); its lattice point is raster_origin's
-// (f3d_raster.h) with lift 0,
-//     g = (plane_at(origin_x, i, spacing_x), h(i, j), plane_at(origin_z, j, spacing_z)).
+// Sample n of the region is DEM sample (j, i); g = (x_i, h(i, j), z_j) is its lattice point: lattice_point (f3d_walk.h), lift 0.
 // An observer is four f32 (x, Y, z, w), as a TOWARD_POINT target of f3d_session_raster; w > 0 is a maximum horizontal
 // distance.  With dx = x - g.x, dz = z - g.z, hd2 = dx dx + dz dz and k = hd2 inv_two_r_prime under the curvature policy
 // (CURVED on a scene whose curvature is enabled; else 0), raster_visible at lift L marches a ray whose height at parameter
@@ -120,6 +118,23 @@ F3D_HD float clearance_height(const ClearanceParams &R, V3 g, uint32_t i, uint32
     if (H != H) return nan;
     const float L = ((ob.y + k) - g.y) + H;
     return L > 0.0f ? L : 0.0f;
+}
+
+// One lane, sample n of the region (what k_clearance calls): every observer's plane, and the minimum over the observers.
+// With height null nothing of size observer_count x rows * cols exists anywhere.
+template <class Levels>
+F3D_HD void clearance_lane(const ClearanceParams R, uint32_t n, const Levels &levels) {
+    const uint32_t total = R.rows * R.cols;
+    uint32_t i, j;
+    const V3 g = clearance_sample(R, n, i, j);
+    float lowest = __builtin_inff();
+    for (uint32_t k = 0u; k < R.observer_count; k++) {
+        const float4 observer = R.observers[k];
+        const float L = clearance_height(R, g, i, j, observer, levels);
+        if (R.height) R.height[(size_t)k * total + n] = L;
+        lowest = f_min(lowest, L);  // (a NaN plane is ignored)
+    }
+    if (R.lowest) R.lowest[n] = lowest;
 }
 
 }  // namespace f3d

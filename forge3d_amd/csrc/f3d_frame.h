@@ -881,11 +881,13 @@ __global__ __launch_bounds__(kWave) void k_raster(const RasterParams R) {
     if (R.count && have) R.count[n] = seen;
 }
 
-// Horizon rasters on a live session (f3d_session_horizon; f3d_horizon.h): one wave a workgroup, one lane a DEM sample of the
-// region -- 64 consecutive samples (the planes are written 256 contiguous bytes a wave), or with R.block an 8 x 8 block of the
-// region (the 64 lines of an azimuth stay together at the coarse levels; measured: profiles/README.md).  The lane keeps its
-// sample's origin and its sky-view sum in registers across the azimuths; the walk has no wave primitive in it, and all it
-// needs of LDS is the per-level layout of the band table (128 bytes).
+// Horizon, clearance and shadow-depth rasters on a live session (f3d_session_horizon / _clearance / _umbra; f3d_horizon.h,
+// f3d_clearance.h, f3d_umbra.h): one wave a workgroup, one lane a DEM sample of the region -- region_sample (f3d_walk.h), with
+// R.block an 8 x 8 block of it.  A kernel is the opening below and its family's lane body (*_lane; k_umbra's stands in the
+// kernel, see there: the loop over the azimuths,
+// observers or directions is wave-uniform and every lane reads them at the same address; the lane keeps its sample and its sum,
+// minimum or maximum in registers and writes what it owns with ordinary stores).  The walk has no wave primitive in it, and all
+// it needs of LDS is the per-level layout of the band table (128 bytes).
 struct HorizonLevels {
     const uint32_t *table;  // {band_offset, band_shift} per level
     __device__ __forceinline__ void band_entry(const TerrainDev &, uint32_t level, uint32_t &offset, uint32_t &shift) const {
@@ -894,7 +896,7 @@ struct HorizonLevels {
         shift = e.y;
     }
 };
-// The opening k_horizon and k_clearance share.  The band table's per-level layout into the workgroup's 128 bytes of LDS:
+// The band table's per-level layout into the workgroup's 128 bytes of LDS:
 __device__ __forceinline__ void load_level_table(uint32_t *table, const TerrainDev &terrain) {
     if (threadIdx.x < kMaxLevels) {
         table[2u * threadIdx.x] = terrain.band_offset[threadIdx.x];
@@ -902,75 +904,31 @@ __device__ __forceinline__ void load_level_table(uint32_t *table, const TerrainD
     }
     __syncthreads();
 }
-// (workgroup, lane) -> sample n of a rows x cols region: 64 consecutive samples a wave, or with `block` an 8 x 8 block of
-// the region.  false: the lane has no sample.
-__device__ __forceinline__ bool lane_sample(uint32_t rows, uint32_t cols, uint32_t block, uint32_t &n) {
-    n = blockIdx.x * kWave + threadIdx.x;
-    bool have = n < rows * cols;
-    if (block != 0u) {
-        const uint32_t tiles_x = (cols + 7u) >> 3;
-        const uint32_t r = (blockIdx.x / tiles_x) * 8u + (threadIdx.x >> 3), c = (blockIdx.x % tiles_x) * 8u + (threadIdx.x & 7u);
-        have = r < rows && c < cols;
-        n = r * cols + c;
-    }
-    return have;
+// The opening: the level table, then the lane's sample n.  false: the lane has no sample (no wave primitive follows).
+template <class Params>
+__device__ __forceinline__ bool region_open(const Params &R, uint32_t *table, uint32_t &n) {
+    load_level_table(table, R.terrain);
+    return region_sample(R.rows, R.cols, R.block, blockIdx.x, threadIdx.x, n);
 }
 __global__ __launch_bounds__(kWave) void k_horizon(const HorizonParams R) {
     __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
-    load_level_table(table, R.terrain);
-    const HorizonLevels levels{table};
-    const uint32_t total = R.rows * R.cols;
     uint32_t n;
-    if (!lane_sample(R.rows, R.cols, R.block, n)) return;  // (no wave primitive below)
-    uint32_t i, j;
-    const V3 o = horizon_origin(R, n, i, j);
-    float sum = 0.0f;
-    for (uint32_t k = 0u; k < R.azimuth_count; k++) {
-        const float2 az = R.azimuths[k];
-        const float H = horizon_walk(R.terrain, o, i, j, az.x, az.y, horizon_curvature(R, az.x, az.y), R.step_cap, levels);
-        if (R.horizon) R.horizon[(size_t)k * total + n] = H;
-        sum = sum + horizon_sky_term(H, az.x, az.y);
-    }
-    if (R.sky_view) R.sky_view[n] = 1.0f - sum / (float)R.azimuth_count;
+    if (region_open(R, table, n)) horizon_lane(R, n, HorizonLevels{table});
 }
-
-// Clearance rasters on a live session (f3d_session_clearance; f3d_clearance.h): k_horizon's shape -- one wave a workgroup, one
-// lane a DEM sample of the region (64 consecutive samples, or with R.block an 8 x 8 block: measured, profiles/README.md), the
-// band table's per-level layout in 128 bytes of LDS.  The loop over the observers is wave-uniform and every lane reads the
-// observer at the same address; the lane keeps its sample and the minimum over the observers in registers and writes what it
-// owns with ordinary stores.  With height null nothing of size observer_count x rows * cols exists anywhere.
 __global__ __launch_bounds__(kWave) void k_clearance(const ClearanceParams R) {
     __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
-    load_level_table(table, R.terrain);
-    const HorizonLevels levels{table};
-    const uint32_t total = R.rows * R.cols;
     uint32_t n;
-    if (!lane_sample(R.rows, R.cols, R.block, n)) return;  // (no wave primitive below)
-    uint32_t i, j;
-    const V3 g = clearance_sample(R, n, i, j);
-    float lowest = __builtin_inff();
-    for (uint32_t k = 0u; k < R.observer_count; k++) {
-        const float4 observer = R.observers[k];
-        const float L = clearance_height(R, g, i, j, observer, levels);
-        if (R.height) R.height[(size_t)k * total + n] = L;
-        lowest = f_min(lowest, L);  // (a NaN plane is ignored)
-    }
-    if (R.lowest) R.lowest[n] = lowest;
+    if (region_open(R, table, n)) clearance_lane(R, n, HorizonLevels{table});
 }
-
-// Shadow-depth rasters on a live session (f3d_session_umbra; f3d_umbra.h): k_clearance's shape -- one wave a workgroup, one
-// lane a DEM sample of the region (64 consecutive samples, or with R.block an 8 x 8 block: measured, profiles/README.md), the
-// band table's per-level layout in 128 bytes of LDS.  The loop over the directions is wave-uniform and every lane reads the
-// direction at the same address (none: the session's sun, one direction); the lane keeps its sample and the maximum over the
-// directions in registers and writes what it owns with ordinary stores.  With depth null nothing of size direction_count x
-// rows * cols exists anywhere.
+// k_umbra keeps its lane body in the kernel (directions null: the session's sun, one direction; with depth null nothing of size
+// direction_count x rows * cols exists anywhere): as a function called with the Params, by value or by reference, the same text
+// compiles to another schedule that measures 0.4 % slower over 16 directions (profiles/README.md, "Raster lanes refactor").
 __global__ __launch_bounds__(kWave) void k_umbra(const UmbraParams R) {
     __shared__ __attribute__((aligned(8))) uint32_t table[2 * kMaxLevels];
-    load_level_table(table, R.terrain);
+    uint32_t n;
+    if (!region_open(R, table, n)) return;
     const HorizonLevels levels{table};
     const uint32_t total = R.rows * R.cols;
-    uint32_t n;
-    if (!lane_sample(R.rows, R.cols, R.block, n)) return;  // (no wave primitive below)
     uint32_t i, j;
     const V3 g = umbra_sample(R, n, i, j);
     float deepest = 0.0f;

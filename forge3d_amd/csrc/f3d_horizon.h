@@ -1,9 +1,7 @@
 // forge3d_amd/csrc/f3d_horizon.h -- horizon rasters on a live session (f3d_session_horizon): what one lane of k_horizon does.
 //
-// THE CONTRACT.  Terrain only: a session with a mesh answers for the ground.  Sample n = r * cols + c of the region is DEM
-// sample (j = row0 + r, i = col0 + c) and stands on the lifted lattice point of the visibility rasters (f3d_raster.h
-// raster_origin: the same corner of the leaf table's record, the same plane_at, the same lift; lift >= 0 here)
-//     o = (plane_at(origin_x, i, spacing_x), h(i, j) + lift, plane_at(origin_z, j, spacing_z)).
+// THE CONTRACT.  Terrain only: a session with a mesh answers for the ground.  Sample n of the region is DEM sample (j, i) and
+// stands on o = (x_i, h(i, j) + lift, z_j), the visibility rasters' lifted lattice point (lattice_point, f3d_walk.h; lift >= 0).
 // An azimuth is a horizontal direction (dx, dz), f32, used as given.  With p(t) = (o.x + t dx, o.z + t dz) and y(p) the
 // bilinear surface of the cell under p (the leaf record's four corners), the horizon of the sample along the azimuth is
 //     H = sup over t > 0 with p(t) inside the DEM's footprint of ( y(p(t)) - k t^2 - o.y ) / t
@@ -85,6 +83,22 @@ template <class Levels>
 F3D_HD float horizon_walk(const TerrainDev &T, V3 o, uint32_t i, uint32_t j, float dx, float dz, float k, uint32_t cap, const Levels &levels) {
     if (!(f_finite(dx) && f_finite(dz)) || (dx == 0.0f && dz == 0.0f)) return f_from_bits(0x7FC00000u);
     return pyramid_walk(T, o.x, o.z, dx, dz, i, j, cap, levels, HorizonPolicy(T, o.y, i, j, dx, dz, k));
+}
+
+// One lane, sample n of the region (what k_horizon calls): every azimuth's plane, and the sky view.  No wave primitive.
+template <class Levels>
+F3D_HD void horizon_lane(const HorizonParams R, uint32_t n, const Levels &levels) {
+    const uint32_t total = R.rows * R.cols;
+    uint32_t i, j;
+    const V3 o = horizon_origin(R, n, i, j);
+    float sum = 0.0f;
+    for (uint32_t k = 0u; k < R.azimuth_count; k++) {
+        const float2 az = R.azimuths[k];
+        const float H = horizon_walk(R.terrain, o, i, j, az.x, az.y, horizon_curvature(R, az.x, az.y), R.step_cap, levels);
+        if (R.horizon) R.horizon[(size_t)k * total + n] = H;
+        sum = sum + horizon_sky_term(H, az.x, az.y);
+    }
+    if (R.sky_view) R.sky_view[n] = 1.0f - sum / (float)R.azimuth_count;
 }
 
 }  // namespace f3d

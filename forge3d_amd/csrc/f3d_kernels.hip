@@ -211,32 +211,21 @@ hipError_t launch_raster(const RasterParams &p, hipStream_t stream) {
     with_mesh(has_mesh(p.frame), [&](auto M) { hipLaunchKernelGGL((k_raster<M()>), grid, block, 0, stream, p); });
     return hipGetLastError();
 }
-hipError_t launch_horizon(const HorizonParams &p, hipStream_t stream) {
-    const uint32_t total = p.rows * p.cols;
-    if (total == 0u || p.azimuth_count == 0u) return hipSuccess;
-    const uint32_t waves = p.block ? ((p.cols + 7u) >> 3) * ((p.rows + 7u) >> 3) : (total + kWave - 1u) / kWave;
-    hipLaunchKernelGGL(k_horizon, dim3(waves), dim3(kWave), 0, stream, p);
+// k_horizon, k_clearance, k_umbra: one wave a workgroup over the region's waves; `count` planes, none: nothing to do
+template <class Params>
+static hipError_t launch_region(void (*kernel)(Params), const Params &p, uint32_t count, hipStream_t stream) {
+    if (p.rows * p.cols == 0u || count == 0u) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3(region_waves(p.rows, p.cols, p.block)), dim3(kWave), 0, stream, p);
     return hipGetLastError();
 }
+hipError_t launch_horizon(const HorizonParams &p, hipStream_t stream) { return launch_region(k_horizon, p, p.azimuth_count, stream); }
+hipError_t launch_clearance(const ClearanceParams &p, hipStream_t stream) { return launch_region(k_clearance, p, p.observer_count, stream); }
+hipError_t launch_umbra(const UmbraParams &p, hipStream_t stream) { return launch_region(k_umbra, p, p.direction_count, stream); }
 hipError_t launch_irradiation(const IrradiationParams &p, hipStream_t stream) {
     const uint32_t total = p.rows * p.cols;
     if (total == 0u) return hipSuccess;
     const dim3 grid((total + kWave - 1u) / kWave), block(kWave);
     with_mesh(has_mesh(p.frame), [&](auto M) { hipLaunchKernelGGL((k_irradiation<M()>), grid, block, 0, stream, p); });
-    return hipGetLastError();
-}
-hipError_t launch_clearance(const ClearanceParams &p, hipStream_t stream) {
-    const uint32_t total = p.rows * p.cols;
-    if (total == 0u || p.observer_count == 0u) return hipSuccess;
-    const uint32_t waves = p.block ? ((p.cols + 7u) >> 3) * ((p.rows + 7u) >> 3) : (total + kWave - 1u) / kWave;
-    hipLaunchKernelGGL(k_clearance, dim3(waves), dim3(kWave), 0, stream, p);
-    return hipGetLastError();
-}
-hipError_t launch_umbra(const UmbraParams &p, hipStream_t stream) {
-    const uint32_t total = p.rows * p.cols;
-    if (total == 0u || p.direction_count == 0u) return hipSuccess;
-    const uint32_t waves = p.block ? ((p.cols + 7u) >> 3) * ((p.rows + 7u) >> 3) : (total + kWave - 1u) / kWave;
-    hipLaunchKernelGGL(k_umbra, dim3(waves), dim3(kWave), 0, stream, p);
     return hipGetLastError();
 }
 hipError_t launch_leaf_build(const PyramidBuildParams &p, hipStream_t stream) {

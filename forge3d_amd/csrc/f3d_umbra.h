@@ -6,9 +6,7 @@
 // THE CONTRACT.  Terrain only: a session with a mesh answers for its ground, as the horizon and clearance rasters do.  All
 // arithmetic is f32, one rounding per written operation (f3d_math.h), so the host build (tests/umbra_host) and the device return
 // the same bits.
-// Sample n = r * cols + c of the region is DEM sample (j = row0 + r, i = col0 + c); its lattice point is lattice_point's
-// (f3d_walk.h) with lift 0,
-//     g = (plane_at(origin_x, i, spacing_x), h(i, j), plane_at(origin_z, j, spacing_z)).
+// Sample n of the region is DEM sample (j, i); g = (x_i, h(i, j), z_j) is its lattice point: lattice_point (f3d_walk.h), lift 0.
 // A direction is four f32 (dx, dy, dz, w), used as given, not normalised: toward the light, as an ALONG_DIRECTION target of
 // f3d_session_raster.  w is reserved: 0.  With p(t) = (g.x + t dx, g.z + t dz), y(p) the bilinear surface of the cell under p
 // and k = (dx^2 + dz^2) inv_two_r_prime under the curvature policy (CURVED on a scene whose curvature is enabled:

@@ -1,6 +1,8 @@
 // forge3d_amd/csrc/f3d_walk.h -- what the raster lanes share: the lattice point a DEM sample stands on (all five raster
-// families) and the stackless walk over the min-max pyramid under the horizon, clearance and shadow-depth lanes
-// (f3d_horizon.h, f3d_clearance.h, f3d_umbra.h: each a policy of pyramid_walk).
+// families), the samples a wave owns (region_sample) and the stackless walk over the min-max pyramid under the horizon,
+// clearance and shadow-depth lanes (f3d_horizon.h, f3d_clearance.h, f3d_umbra.h: each a policy of pyramid_walk; horizon_lane
+// and clearance_lane are the lane bodies the kernel and the host harness both call, with the Params by value, as the kernel
+// holds them -- a reference costs scalar registers; k_umbra's loop stands in the kernel: profiles/README.md).
 //
 // All arithmetic is f32, one rounding per written operation (f3d_math.h), so the host builds (tests/*_host) and the device
 // return the same bits.
@@ -78,6 +80,25 @@ F3D_HD V3 lattice_point(const TerrainDev &T, uint32_t row0, uint32_t col0, uint3
     j = row0 + r;
     i = col0 + c;
     return V3{plane_at(T.origin_x, i, T.spacing_x), lattice_height(T, i, j) + lift, plane_at(T.origin_z, j, T.spacing_z)};
+}
+
+// A wave's samples (k_horizon, k_clearance, k_umbra: one wave a workgroup, one lane a sample): lane `lane` of wave `wave` ->
+// sample n of a rows x cols region.  A wave owns 64 consecutive samples (the planes are written 256 contiguous bytes a wave),
+// or with `block` an 8 x 8 block of the region (the 64 lines of an azimuth stay together at the coarse levels; measured:
+// profiles/README.md).  false: the lane has no sample.  region_waves: the waves that cover the region, the launch's grid.
+F3D_HD bool region_sample(uint32_t rows, uint32_t cols, uint32_t block, uint32_t wave, uint32_t lane, uint32_t &n) {
+    n = wave * 64u + lane;
+    bool have = n < rows * cols;
+    if (block != 0u) {
+        const uint32_t tiles_x = (cols + 7u) >> 3;
+        const uint32_t r = (wave / tiles_x) * 8u + (lane >> 3), c = (wave % tiles_x) * 8u + (lane & 7u);
+        have = r < rows && c < cols;
+        n = r * cols + c;
+    }
+    return have;
+}
+F3D_HD uint32_t region_waves(uint32_t rows, uint32_t cols, uint32_t block) {
+    return block != 0u ? ((cols + 7u) >> 3) * ((rows + 7u) >> 3) : (rows * cols + 63u) >> 6;
 }
 
 // the walk's step cap: every lattice line the line can cross, four times over, plus eight trips through the levels

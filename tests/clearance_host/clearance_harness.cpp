@@ -1,9 +1,8 @@
 // tests/clearance_host/clearance_harness.cpp -- TEST INFRASTRUCTURE ONLY (tests/test_session_clearance_host.py compiles it).
-// The clearance rasters' lane body (f3d_clearance.h clearance_sample / clearance_height / clearance_walk, what k_clearance
-// runs per lane) on the host over whole 64-lane waves, with k_clearance's two footprints: wave b owns samples
-// [64 b, 64 b + 64) of the region, or an 8 x 8 block of it.  The walk has no wave primitive in it, so a wave is a plain loop
-// over its lanes; the loop over the observers and the minimum are written as the kernel writes them.  `cap`
-// (0: clearance_step_cap) injects a tiny step cap -- here only, the library has no such switch.
+// The clearance rasters' lane body (f3d_clearance.h clearance_lane, what k_clearance calls per lane) on the host over the
+// waves and lanes k_clearance is launched with (f3d_walk.h region_waves / region_sample, both footprints).  The walk has no
+// wave primitive in it, so a wave is a plain loop over its lanes.  `cap` (0: clearance_step_cap) injects a tiny step cap --
+// here only, the library has no such switch.
 // With -DCLEARANCE_DRIVER the file is a stand-alone program (its own main) over two synthetic DEMs, for a sanitizer build.
 #include "../emul/f3d_emul.cpp"
 #include "../emul/host_scene.h"
@@ -23,65 +22,29 @@ void run_clearance(const TerrainDev &T, uint32_t flags, uint32_t row0, uint32_t 
     R.observer_count = count;
     R.step_cap = cap ? cap : clearance_step_cap(T);
     R.block = block;
-    const uint32_t total = rows * cols, tiles_x = (cols + 7u) >> 3;
-    const long waves = block ? (long)tiles_x * ((rows + 7u) >> 3) : ((long)total + 63) / 64;
-    const DirectLevels levels;
+    R.observers = (const float4 *)observers;
+    R.height = height;
+    R.lowest = lowest;
+    const long waves = region_waves(rows, cols, block);
 #pragma omp parallel for schedule(dynamic, 1)
     for (long wv = 0; wv < waves; wv++)
-        for (uint32_t lane = 0; lane < 64u; lane++) {
-            uint32_t n = (uint32_t)wv * 64u + lane;
-            bool have = n < total;
-            if (block) {
-                const uint32_t r = ((uint32_t)wv / tiles_x) * 8u + (lane >> 3), c = ((uint32_t)wv % tiles_x) * 8u + (lane & 7u);
-                have = r < rows && c < cols;
-                n = r * cols + c;
+        for (uint32_t lane = 0, n, i, j; lane < 64u; lane++)
+            if (region_sample(rows, cols, block, (uint32_t)wv, lane, n)) {
+                clearance_lane(R, n, DirectLevels{});
+                store_point(samples, n, clearance_sample(R, n, i, j));
             }
-            if (!have) continue;
-            uint32_t i, j;
-            const V3 g = clearance_sample(R, n, i, j);
-            if (samples) {
-                samples[3u * (size_t)n] = g.x;
-                samples[3u * (size_t)n + 1u] = g.y;
-                samples[3u * (size_t)n + 2u] = g.z;
-            }
-            float low = __builtin_inff();
-            for (uint32_t k = 0u; k < count; k++) {
-                const float4 observer{observers[4u * k], observers[4u * k + 1u], observers[4u * k + 2u], observers[4u * k + 3u]};
-                const float L = clearance_height(R, g, i, j, observer, levels);
-                if (height) height[(size_t)k * total + n] = L;
-                low = f_min(low, L);
-            }
-            if (lowest) lowest[n] = low;
-        }
 }
 }  // namespace
 
-// info[0..5] = terrain origin x, origin z, spacing x, spacing z, inv_two_r_prime, curvature_enabled
-extern "C" void *clearance_scene_create(const f3d_terrain_ref_desc *d, float *info) {
-    HostScene *S = new HostScene();
-    try {
-        setup(*S, d, 1, 0u, 0u);
-    } catch (const Failure &) {
-        delete S;
-        return nullptr;
-    }
-    if (info) {
-        info[0] = S->P.terrain.origin_x;
-        info[1] = S->P.terrain.origin_z;
-        info[2] = S->P.terrain.spacing_x;
-        info[3] = S->P.terrain.spacing_z;
-        info[4] = S->P.terrain.inv_two_r_prime;
-        info[5] = (float)S->P.terrain.curvature_enabled;
-    }
-    return S;
-}
-
+// info[0..5]: scene_create's first six (tests/emul/host_scene.h)
+extern "C" void *clearance_scene_create(const f3d_terrain_ref_desc *d, float *info) { return scene_create(d, 1, info, 6u); }
 extern "C" void clearance_scene_destroy(void *scene) { delete (HostScene *)scene; }
 
 // One clearance raster as f3d_session_clearance's device form answers it (flags: 2 CURVED).  height (count x rows * cols),
 // lowest (rows * cols) and samples (rows * cols x 3: the lattice points) may each be null.
 extern "C" int clearance_run(void *scene, uint32_t flags, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols, uint32_t count,
                              const float *observers, float *height, float *lowest, float *samples, uint32_t cap, uint32_t block) {
+    if ((uintptr_t)observers % alignof(float4) != 0u) return 2;  // (read as float4: a NumPy allocation is aligned, an odd view is not)
     run_clearance(((const HostScene *)scene)->P.terrain, flags, row0, col0, rows, cols, count, observers, height, lowest, samples, cap, block);
     return 0;
 }
@@ -99,24 +62,13 @@ int main() {
     const uint32_t shapes[2][2] = {{65u, 63u}, {5u, 3u}};
     for (const auto &shape : shapes) {
         const uint32_t w = shape[0], h = shape[1];
-        std::vector<float> dem((size_t)w * h);
-        for (uint32_t z = 0; z < h; z++)
-            for (uint32_t x = 0; x < w; x++) dem[(size_t)z * w + x] = 3.0f * std::sin(0.37f * (float)x) * std::cos(0.23f * (float)z) + 0.05f * (float)((x * 7u + z * 13u) % 11u);
-        HostTables t = build_tables_host(dem.data(), w, h, 20.0f);
+        HostTables t;
         TerrainDev T{};
-        t.attach(T);
-        T.spacing_x = 30.0f;
-        T.spacing_z = 25.0f;
-        T.inv_spacing_x = 1.0f / T.spacing_x;
-        T.inv_spacing_z = 1.0f / T.spacing_z;
-        T.origin_x = -0.5f * ((float)w - 1.0f) * T.spacing_x;
-        T.origin_z = -0.5f * ((float)h - 1.0f) * T.spacing_z;
-        T.inv_two_r_prime = 6.7e-8f;
-        T.curvature_enabled = 1u;
+        driver_terrain(w, h, t, T);
         const float x_mid = plane_at(T.origin_x, w / 2u, T.spacing_x), z_last = plane_at(T.origin_z, h - 1u, T.spacing_z);
         const float z_row = plane_at(T.origin_z, h / 2u, T.spacing_z);
         const float nan = f_from_bits(0x7FC00000u);
-        const float observers[] = {
+        alignas(16) const float observers[] = {
             0.3f * T.origin_x, 150.0f, 0.2f * T.origin_z, 0.0f,    // high over the footprint
             -0.2f * T.origin_x, 120.0f, 0.1f * T.origin_z, 400.0f,  // a distance limit
             1.4f * T.origin_x, 90.0f, -0.3f * T.origin_z, 0.0f,     // outside the footprint

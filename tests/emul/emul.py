@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -27,11 +28,20 @@ CXX = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-march=x86-6
 
 def build_harness(source: Path, name: str) -> C.CDLL:
     """A host harness (tests/*_host/*.cpp: the emulator plus its own entry points) built in a fresh directory and loaded."""
-    import tempfile
-
     out = Path(tempfile.mkdtemp(prefix=f"f3d_{name}_")) / f"lib{name}.so"
     subprocess.run([*CXX, str(source), "-o", str(out)], check=True, capture_output=True)
     return C.CDLL(str(out))
+
+
+def run_sanitized_driver(source: Path, name: str) -> subprocess.CompletedProcess:
+    """A host harness built with -D<NAME>_DRIVER as a stand-alone program (its own main, never code loaded into this process)
+    under the address and undefined-behaviour sanitizers, and run once; the build must succeed, the run is the caller's to judge."""
+    out = Path(tempfile.mkdtemp(prefix=f"f3d_{name}_driver_")) / f"{name}_driver"
+    flags = [f for f in CXX if f not in ("-shared", "-fPIC", "-O2")]
+    build = subprocess.run([*flags, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", f"-D{name.upper()}_DRIVER", str(source),
+                            "-o", str(out)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    return subprocess.run([str(out)], capture_output=True, text=True, env={"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1"})
 
 
 def build(force=False):

@@ -48,11 +48,7 @@ void run_irradiation(const FrameParams &P, uint32_t flags, uint32_t row0, uint32
             uint32_t i, j;
             o[l] = irradiation_origin(R, first + l, i, j);
             s[l] = irradiation_slope(R, i, j);
-            if (origins) {
-                origins[3u * (size_t)(first + l)] = o[l].x;
-                origins[3u * (size_t)(first + l) + 1u] = o[l].y;
-                origins[3u * (size_t)(first + l) + 2u] = o[l].z;
-            }
+            store_point(origins, first + l, o[l]);
         }
         for (uint32_t k = 0; k < count; k++) {
             const float4 dir = R.directions[k];
@@ -74,12 +70,7 @@ void run_irradiation(const FrameParams &P, uint32_t flags, uint32_t row0, uint32
         for (uint32_t l = 0; l < n; l++) {
             if (energy) energy[first + l] = sum[l];
             if (seen_out) seen_out[first + l] = seen[l];
-            if (normal) {
-                const V3 nrm = irradiation_normal(s[l]);
-                normal[3u * (size_t)(first + l)] = nrm.x;
-                normal[3u * (size_t)(first + l) + 1u] = nrm.y;
-                normal[3u * (size_t)(first + l) + 2u] = nrm.z;
-            }
+            store_point(normal, first + l, irradiation_normal(s[l]));
         }
     }
 }
@@ -88,28 +79,7 @@ void run_irradiation(const FrameParams &P, uint32_t flags, uint32_t row0, uint32
 // One irradiation raster as f3d_session_irradiation's device form answers it, over a scene made by the raster harness's
 // raster_scene_create (tests/raster_host: the same HostScene).  marches (count x rows * cols words, may be null): how many
 // terrain marches the lane of sample n entered for direction k.
-extern "C" void *irradiation_scene_create(const f3d_terrain_ref_desc *d, int32_t mesh_form, float *info) {
-    HostScene *S = new HostScene();
-    try {
-        setup(*S, d, mesh_form == 2 ? 2 : 1, 0u, 0u);
-    } catch (const Failure &) {
-        delete S;
-        return nullptr;
-    }
-    if (info) {  // (the raster harness's nine: origin x z, spacing x z, inv_two_r_prime, curvature_enabled, light.wi)
-        info[0] = S->P.terrain.origin_x;
-        info[1] = S->P.terrain.origin_z;
-        info[2] = S->P.terrain.spacing_x;
-        info[3] = S->P.terrain.spacing_z;
-        info[4] = S->P.terrain.inv_two_r_prime;
-        info[5] = (float)S->P.terrain.curvature_enabled;
-        info[6] = S->P.light.wi.x;
-        info[7] = S->P.light.wi.y;
-        info[8] = S->P.light.wi.z;
-    }
-    return S;
-}
-
+extern "C" void *irradiation_scene_create(const f3d_terrain_ref_desc *d, int32_t mesh_form, float *info) { return scene_create(d, mesh_form, info, 9u); }
 extern "C" void irradiation_scene_destroy(void *scene) { delete (HostScene *)scene; }
 
 extern "C" int irradiation_run(void *scene, uint32_t flags, uint32_t row0, uint32_t col0, uint32_t rows, uint32_t cols, float lift, uint32_t count,
@@ -130,21 +100,9 @@ int main() {
     const uint32_t shapes[2][2] = {{65u, 63u}, {5u, 3u}};
     for (const auto &shape : shapes) {
         const uint32_t w = shape[0], h = shape[1];
-        std::vector<float> dem((size_t)w * h);
-        for (uint32_t z = 0; z < h; z++)
-            for (uint32_t x = 0; x < w; x++) dem[(size_t)z * w + x] = 3.0f * std::sin(0.37f * (float)x) * std::cos(0.23f * (float)z) + 0.05f * (float)((x * 7u + z * 13u) % 11u);
-        HostTables t = build_tables_host(dem.data(), w, h, 20.0f);
+        HostTables t;
         FrameParams P{};
-        TerrainDev &T = P.terrain;
-        t.attach(T);
-        T.spacing_x = 30.0f;
-        T.spacing_z = 25.0f;
-        T.inv_spacing_x = 1.0f / T.spacing_x;
-        T.inv_spacing_z = 1.0f / T.spacing_z;
-        T.origin_x = -0.5f * ((float)w - 1.0f) * T.spacing_x;
-        T.origin_z = -0.5f * ((float)h - 1.0f) * T.spacing_z;
-        T.inv_two_r_prime = 6.7e-8f;
-        T.curvature_enabled = 1u;
+        driver_terrain(w, h, t, P.terrain);
         P.mesh.traversal_mode = 3u;
         std::vector<float> dirs;
         for (int k = 0; k < 6; k++) {

@@ -19,30 +19,13 @@ struct RasterPending : WavePending {
 }  // namespace
 
 // mesh_form: 0 the reference's sweep, 1 the threaded binary walk, 2 four children wide.
-// info[0..7] = terrain origin x, origin z, spacing x, spacing z, inv_two_r_prime, curvature_enabled, light.wi x y z (info[6..8])
+// info[0..8]: scene_create's nine (tests/emul/host_scene.h)
 extern "C" void *raster_scene_create(const f3d_terrain_ref_desc *d, int32_t mesh_form, float *info) {
-    HostScene *S = new HostScene();
-    try {
-        setup(*S, d, mesh_form == 2 ? 2 : 1, 0u, 0u);
-    } catch (const Failure &) {
-        delete S;
-        return nullptr;
-    }
-    if (mesh_form == 0) {
+    HostScene *S = scene_create(d, mesh_form, info, 9u);
+    if (S && mesh_form == 0) {
         S->P.mesh.bvh_nodes = nullptr;
         S->P.mesh.bvh4_nodes = nullptr;
         S->P.mesh.bvh_tris = nullptr;
-    }
-    if (info) {
-        info[0] = S->P.terrain.origin_x;
-        info[1] = S->P.terrain.origin_z;
-        info[2] = S->P.terrain.spacing_x;
-        info[3] = S->P.terrain.spacing_z;
-        info[4] = S->P.terrain.inv_two_r_prime;
-        info[5] = (float)S->P.terrain.curvature_enabled;
-        info[6] = S->P.light.wi.x;
-        info[7] = S->P.light.wi.y;
-        info[8] = S->P.light.wi.z;
     }
     return S;
 }
@@ -79,11 +62,7 @@ extern "C" int raster_run(void *scene, uint32_t mode, uint32_t flags, uint32_t r
         uint32_t seen[64] = {};
         for (uint32_t l = 0; l < n; l++) {
             o[l] = raster_origin(R, first + l);
-            if (origins) {
-                origins[3u * (size_t)(first + l)] = o[l].x;
-                origins[3u * (size_t)(first + l) + 1u] = o[l].y;
-                origins[3u * (size_t)(first + l) + 2u] = o[l].z;
-            }
+            store_point(origins, first + l, o[l]);
         }
         for (uint32_t k = 0; k < R.target_count; k++) {
             const float4 target = R.targets ? R.targets[k] : float4{R.frame.light.wi.x, R.frame.light.wi.y, R.frame.light.wi.z, 0.0f};

@@ -1,7 +1,7 @@
 """Clearance rasters on a live terrain session (f3d_session_clearance), the parts that need no GPU.
 
-The lane body of the clearance kernel (csrc/f3d_clearance.h clearance_sample / clearance_height / clearance_walk, what
-k_clearance runs per lane) compiled for the host (tests/clearance_host) and run over whole 64-lane waves, against
+The lane body of the clearance kernel (csrc/f3d_clearance.h clearance_lane, what k_clearance calls per lane) compiled for the
+host (tests/clearance_host) and run over the kernel's waves and lanes (csrc/f3d_walk.h region_sample), against
 tests/clearance_reference.py -- an independent float64 statement of the contract's first form that cuts the sight line at
 every lattice line and knows nothing of the pyramid or the walk.
 
@@ -23,8 +23,6 @@ from __future__ import annotations
 
 import ctypes as C
 import re
-import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -389,12 +387,7 @@ def test_bracket_leaves_out_at_most_two_percent(shaped):
 
 # ---- the sanitizer run: a stand-alone program, never code loaded into this process ---------------------------------------------
 def test_driver_runs_clean_under_address_and_undefined_sanitizers():
-    out = Path(tempfile.mkdtemp(prefix="f3d_clearance_driver_")) / "clearance_driver"
-    flags = [f for f in emul.CXX if f not in ("-shared", "-fPIC", "-O2")]
-    build = subprocess.run([*flags, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DCLEARANCE_DRIVER", str(HARNESS),
-                            "-o", str(out)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(out)], capture_output=True, text=True, env={"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1"})
+    run = emul.run_sanitized_driver(HARNESS, "clearance")
     assert run.returncode == 0, run.stdout[-1000:] + run.stderr[-3000:]
     assert "NaN without an injected cap or a NaN observer: 0" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
 

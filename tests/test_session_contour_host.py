@@ -286,12 +286,7 @@ def test_chain_contours_on_hand_made_inputs():
 
 # ---- the sanitizer run: a stand-alone program, never code loaded into this process ---------------------------------------------
 def test_driver_runs_clean_under_address_and_undefined_sanitizers():
-    out = Path(tempfile.mkdtemp(prefix="f3d_contour_driver_")) / "contour_driver"
-    flags = [f for f in emul.CXX if f not in ("-shared", "-fPIC", "-O2")]
-    build = subprocess.run([*flags, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DCONTOUR_DRIVER", str(cases.HARNESS),
-                            "-o", str(out)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(out)], capture_output=True, text=True, env={"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1"})
+    run = emul.run_sanitized_driver(cases.HARNESS, "contour")
     assert run.returncode == 0, run.stdout[-1000:] + run.stderr[-3000:]
     assert "disagreements: 0" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
 

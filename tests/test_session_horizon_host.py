@@ -1,7 +1,7 @@
 """Horizon rasters on a live terrain session (f3d_session_horizon), the parts that need no GPU.
 
-The lane body of the horizon kernel (csrc/f3d_horizon.h horizon_origin / horizon_walk / horizon_sky_term, what k_horizon
-runs per lane) compiled for the host (tests/horizon_host) and run over whole 64-lane waves, against
+The lane body of the horizon kernel (csrc/f3d_horizon.h horizon_lane, what k_horizon calls per lane) compiled for the host
+(tests/horizon_host) and run over the kernel's waves and lanes (csrc/f3d_walk.h region_sample), against
 tests/horizon_reference.py -- an independent float64 statement of the contract that cuts the line at every lattice line and
 knows nothing of the pyramid or the walk.
 
@@ -21,8 +21,6 @@ from __future__ import annotations
 
 import ctypes as C
 import re
-import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -339,14 +337,20 @@ def test_bracket_leaves_out_at_most_two_percent(shaped):
         assert lit[0] < 0.2 and lit[-1] > 0.8 and all(x < y for x, y in zip(lit, lit[1:])), "the slopes cut through the distribution"
 
 
+# ---- the samples a wave owns: csrc/f3d_walk.h region_sample over region_waves, what the three kernels are launched with --------
+def test_region_sample_hands_out_every_sample_exactly_once(harness):
+    harness.horizon_region_counts.restype = C.c_uint32
+    harness.horizon_region_counts.argtypes = [C.c_uint32] * 3 + [C.c_void_p]
+    for rows, cols in ((1, 1), (1, 65), (65, 1), (7, 9), (8, 8), (9, 17), (63, 65)):
+        for block in (0, 1):
+            counts = np.zeros(rows * cols, np.uint32)
+            outside = harness.horizon_region_counts(rows, cols, block, counts.ctypes.data)
+            assert outside == 0 and (counts == 1).all(), (rows, cols, block, outside, np.flatnonzero(counts != 1)[:8])
+
+
 # ---- the sanitizer run: a stand-alone program, never code loaded into this process ---------------------------------------------
 def test_driver_runs_clean_under_address_and_undefined_sanitizers():
-    out = Path(tempfile.mkdtemp(prefix="f3d_horizon_driver_")) / "horizon_driver"
-    flags = [f for f in emul.CXX if f not in ("-shared", "-fPIC", "-O2")]
-    build = subprocess.run([*flags, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DHORIZON_DRIVER", str(HARNESS),
-                            "-o", str(out)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(out)], capture_output=True, text=True, env={"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1"})
+    run = emul.run_sanitized_driver(HARNESS, "horizon")
     assert run.returncode == 0, run.stdout[-1000:] + run.stderr[-3000:]
     assert "NaN without an injected cap: 0" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
 

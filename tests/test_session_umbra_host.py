@@ -1,7 +1,7 @@
 """Shadow-depth rasters on a live terrain session (f3d_session_umbra), the parts that need no GPU.
 
-The lane body of the umbra kernel (csrc/f3d_umbra.h umbra_sample / umbra_depth / umbra_walk, what k_umbra runs per lane)
-compiled for the host (tests/umbra_host) and run over whole 64-lane waves, against tests/umbra_reference.py -- an independent
+The lane body of the umbra kernel (csrc/f3d_umbra.h umbra_sample / umbra_depth, what k_umbra runs per lane) compiled for the host
+(tests/umbra_host) and run over the kernel's waves and lanes (csrc/f3d_walk.h region_sample), against tests/umbra_reference.py -- an independent
 float64 statement of the contract that cuts the line at every lattice line and knows nothing of the pyramid or the walk.
 
 * DEMs 5x3, 33x33, 64x64 and 65x63 (test_session_raster_host.SHAPES, its spacing and exaggeration), curved and flat; ten
@@ -22,8 +22,6 @@ from __future__ import annotations
 
 import ctypes as C
 import re
-import subprocess
-import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -473,12 +471,7 @@ def test_bracket_leaves_out_at_most_four_percent(shaped):
 
 # ---- the sanitizer run: a stand-alone program, never code loaded into this process ---------------------------------------------
 def test_driver_runs_clean_under_address_and_undefined_sanitizers():
-    out = Path(tempfile.mkdtemp(prefix="f3d_umbra_driver_")) / "umbra_driver"
-    flags = [f for f in emul.CXX if f not in ("-shared", "-fPIC", "-O2")]
-    build = subprocess.run([*flags, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DUMBRA_DRIVER", str(HARNESS),
-                            "-o", str(out)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(out)], capture_output=True, text=True, env={"OMP_NUM_THREADS": "4", "ASAN_OPTIONS": "detect_leaks=1"})
+    run = emul.run_sanitized_driver(HARNESS, "umbra")
     assert run.returncode == 0, run.stdout[-1000:] + run.stderr[-3000:]
     assert "NaN without an injected cap or a bad direction: 0" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
 
