@@ -13,7 +13,8 @@
  * PARITY PIN: the reference (Rust) cannot be built here and ships no golden state for the solver; this oracle is pinned
  * by the reference's own four solver tests restated (sim.rs:801-899: emitter adds the required fields; smoke advects
  * with the wind and preserves mass to 2 %; a buoyant plume rises; the projection reduces the divergence) in
- * tests/test_smoke_sim.py -- "parity pinned by KAT properties only".
+ * tests/test_smoke_sim.py, and held step by step to an independent float64 statement of the step (tests/smoke_sim_reference.py,
+ * tests/test_smoke_sim_reference_host.py) within four times the rounding it shows there.
  * Two deliberate numerical choices (results differ from a Rust build in the last bits either way -- it calls libm):
  *   * sin / cos / exp are the fixed polynomials shared (restated, not included) with the HIP kernels;
  *   * sums over the grid (mass, centroid) are taken row by row, then over the rows of a slab, then over the slabs --
