@@ -292,6 +292,44 @@ CONTOUR_DEVICE_POINTERS = 4
 CONTOUR_MAX_LEVELS = 65536  # F3D_CONTOUR_MAX_LEVELS
 
 
+class DrainageDesc(C.Structure):
+    """f3d_session_drainage_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("direction", C.c_void_p), ("accumulation", C.c_void_p), ("basin", C.c_void_p),
+        ("stats", C.c_void_p), ("ms", C.c_void_p),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class StreamsDesc(C.Structure):
+    """f3d_session_streams_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("threshold", C.c_uint32), ("reserved", C.c_uint32),
+        ("segments", C.c_void_p), ("accumulation", C.c_void_p),
+        ("capacity", C.c_uint64), ("total", C.c_void_p),
+    ]
+
+
+class PaintStreamsDesc(C.Structure):
+    """f3d_session_paint_streams_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("threshold", C.c_uint32), ("reserved", C.c_uint32),
+        ("total", C.c_void_p),
+        ("rgba", C.c_float * 4), ("half_width", C.c_float), ("opacity", C.c_float),
+        ("aim", ReaimDesc),
+    ]
+
+
+DRAINAGE_DEVICE_POINTERS = STREAMS_DEVICE_POINTERS = 4
+DRAINAGE_SINK = 8  # F3D_DRAINAGE_SINK
+
+
 # every symbol include/f3d_terrain_pt.h and include/f3d_wavefront.h declare: (name, restype, argtypes)
 _P = C.POINTER
 ABI = [
@@ -342,6 +380,9 @@ ABI = [
     ("f3d_session_paint_stats", C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint64)]),
     ("f3d_session_contours", C.c_int, [C.c_void_p, _P(ContoursDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_paint_contours", C.c_int, [C.c_void_p, _P(PaintContoursDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_drainage", C.c_int, [C.c_void_p, _P(DrainageDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_streams", C.c_int, [C.c_void_p, _P(StreamsDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_paint_streams", C.c_int, [C.c_void_p, _P(PaintStreamsDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_void_p, C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_sky_blocks", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
@@ -412,7 +453,7 @@ KERNEL_FLAGS = [
     # default is now 1.1 % FASTER, 8 690 -> 8 785 Msamples/s in one call, same image; profiles/r04_variant_ab.log)
 ]
 HIP_SOURCES = ["f3d_kernels.hip", "f3d_host.hip", "f3d_denoise.hip", "f3d_smoke.hip", "f3d_smoke_sim.hip", "f3d_composite.hip", "f3d_lbvh.hip", "f3d_bvh_refit.hip", "f3d_retable.hip", "f3d_wavefront.hip",
-               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip", "f3d_contour.hip"]
+               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip", "f3d_contour.hip", "f3d_drainage.hip"]
 
 
 def source_digest() -> str:

@@ -72,13 +72,16 @@ hipError_t contour_scan_bytes(uint32_t blocks, size_t *bytes) {
                                    rocprim::plus<uint64_t>(), nullptr);
 }
 
+hipError_t launch_contour_scan(const uint64_t *totals, uint64_t *offsets, uint32_t blocks, void *scan_tmp, size_t scan_bytes, hipStream_t stream) {
+    return rocprim::exclusive_scan(scan_tmp, scan_bytes, totals, offsets, (uint64_t)0u, (size_t)blocks + 1u, rocprim::plus<uint64_t>(), stream);
+}
+
 hipError_t launch_contour_count(const ContourParams &P, void *scan_tmp, size_t scan_bytes, hipStream_t stream) {
     const uint32_t blocks = P.nbx * P.nbz;
     hipLaunchKernelGGL(k_contour_count, dim3(blocks + 1u), dim3(64), 0, stream, P);
     const hipError_t launched = hipGetLastError();
     if (launched != hipSuccess) return launched;
-    return rocprim::exclusive_scan(scan_tmp, scan_bytes, (const uint64_t *)P.totals, (uint64_t *)P.offsets, (uint64_t)0u, (size_t)blocks + 1u,
-                                   rocprim::plus<uint64_t>(), stream);
+    return launch_contour_scan(P.totals, (uint64_t *)P.offsets, blocks, scan_tmp, scan_bytes, stream);
 }
 
 hipError_t launch_contour_emit(const ContourParams &P, hipStream_t stream) {

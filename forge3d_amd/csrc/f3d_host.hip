@@ -1023,6 +1023,7 @@ void render_loop(f3d_session &s, f3d_terrain_ref_out *out) {
 #include "f3d_host_drape.h"  // an image draped over the terrain of a live session: checks, buffer, staged upload, packing and its C ABI
 #include "f3d_host_paint.h"  // vector features painted into that drape: checks, records, binning, the paint kernel, the read-back and their C ABI
 #include "f3d_host_contour.h"  // contour lines of the terrain: the query, and the update that emits them into the paint's buffer; their C ABI
+#include "f3d_host_drainage.h"  // drainage of the terrain: directions, accumulation, basins, the stream network extracted or painted; their C ABI
 
 // ---------------------------------------------------------------------------------------
 // C ABI

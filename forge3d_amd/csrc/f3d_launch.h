@@ -63,6 +63,17 @@ struct ContourParams;
 hipError_t contour_scan_bytes(uint32_t blocks, size_t *bytes);
 hipError_t launch_contour_count(const ContourParams &p, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
 hipError_t launch_contour_emit(const ContourParams &p, hipStream_t stream);
+// ... and that scan on its own: the exclusive scan of blocks + 1 totals into offsets (the stream network's waves use it too)
+hipError_t launch_contour_scan(const uint64_t *totals, uint64_t *offsets, uint32_t blocks, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
+// drainage of a session's terrain (f3d_drainage.h, f3d_drainage.hip): the direction pass (clears P.counters first); one doubling
+// round P.round from (P.q, P.s) into (P.q_next, P.s_next); the region out of the final planes; the stream network's count pass +
+// the scan above over stream_waves() + 1 totals, and its emit pass into P.segments / P.stream_accumulation or P.prims
+struct DrainParams;
+hipError_t launch_drain_direction(const DrainParams &p, hipStream_t stream);
+hipError_t launch_drain_round(const DrainParams &p, hipStream_t stream);
+hipError_t launch_drain_write(const DrainParams &p, hipStream_t stream);
+hipError_t launch_stream_count(const DrainParams &p, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
+hipError_t launch_stream_emit(const DrainParams &p, hipStream_t stream);
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream);
 hipError_t launch_query(const QueryParams &p, hipStream_t stream);  // ray queries on a live session (f3d_query.h), 64 rays a workgroup
 hipError_t launch_raster(const RasterParams &p, hipStream_t stream);  // DEM visibility rasters (f3d_raster.h), 64 consecutive samples a workgroup

@@ -618,6 +618,160 @@ class TerrainSession:
         self._update(self._lib.f3d_session_paint_contours, q, q.aim.arm, camera)  # (lv lives until here)
         return int(total.value)
 
+    # -- drainage: flow directions, accumulation, basins, the stream network, on the GPU -------------------
+    DRAINAGE_SINK = _native.DRAINAGE_SINK
+    # (d_row, d_col) of the direction codes 0 .. 7: E, SE, S, SW, W, NW, N, NE (+col east, +row south); code 8 is a sink
+    DRAINAGE_STEPS = ((0, 1), (1, 1), (1, 0), (1, -1), (0, -1), (-1, -1), (-1, 0), (-1, 1))
+    _DRAINAGE_PLANES = (("direction", np.uint8, "torch.uint8"), ("accumulation", np.uint32, "torch.int32"), ("basin", np.uint32, "torch.int32"))
+
+    def drainage(self, region=None, *, direction=True, accumulation=True, basin=False, out=None, wait=True):
+        """Where water goes over the terrain this session renders, routed on the GPU from its own tables (f3d_session_drainage):
+        D8 flow directions -- ``"direction"``, uint8 codes 0 .. 7 = E, SE, S, SW, W, NW, N, NE (DRAINAGE_STEPS), 8 a sink: the
+        steepest positive float32 slope, ties to the lowest code; pits, flats and the border's outlets are sinks --, flow
+        ``"accumulation"``, uint32: the samples whose path passes through a sample, itself included, and ``"basin"``, uint32: the
+        linear index ``row * dem_width + col`` of the sink a sample drains to.  No depressions are filled and no flats
+        resolved.  The whole DEM is routed by every call, from the tables as reterrain() left them; ``region``
+        (``(row0, col0, rows, cols)`` in samples, default the whole DEM) selects what is returned, as arrays (rows, cols).
+        Returns a dict of the planes asked for and always ``"sinks"`` (of the whole DEM), ``"rounds"`` (the path-doubling rounds
+        the accumulation took: ``floor(log2(longest)) + 1``) and ``"longest"`` (the longest path, in steps).
+        ``out=None`` returns NumPy arrays; ``out="device"``, or a dict of contiguous tensors (rows, cols) on the session's
+        device under the planes' names (uint8, int32, int32), takes the device form: nothing crosses the bus but the
+        counters.  The call always waits (a counter is read back after every round): ``wait=False`` is refused."""
+        if not wait:
+            raise ValueError("drainage() always waits: a counter crosses the bus after every doubling round, so there is no wait=False form")
+        row0, col0, rows, cols = self._region(region)
+        want = {"direction": bool(direction), "accumulation": bool(accumulation), "basin": bool(basin)}
+        q = _native.DrainageDesc()
+        q.struct_size = C.sizeof(_native.DrainageDesc)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        stats = (C.c_uint32 * 3)()
+        q.stats = C.addressof(stats)
+        got = {}
+        if out is None:
+            for name, dtype, _ in self._DRAINAGE_PLANES:
+                if want[name]:
+                    got[name] = np.zeros((rows, cols), dtype)
+                    setattr(q, name, got[name].ctypes.data if got[name].size else None)
+        else:
+            import torch
+
+            given = {} if isinstance(out, str) else dict(out)
+            if (isinstance(out, str) and out != "device") or set(given) - set(want):
+                raise ValueError("out must be None, 'device' or a dict of tensors under 'direction', 'accumulation', 'basin'")
+            device = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+            for name, _, tdtype in self._DRAINAGE_PLANES:
+                if name in given:
+                    t = given[name]
+                    if (not _is_tensor(t) or not t.is_cuda or tuple(t.shape) != (rows, cols) or not t.is_contiguous() or str(t.dtype) != tdtype):
+                        raise ValueError(f"out[{name!r}] must be a contiguous {tdtype} tensor ({rows}, {cols}) on the session's device")
+                elif want[name]:
+                    t = torch.empty((rows, cols), dtype=getattr(torch, tdtype.split(".")[1]), device=device)
+                else:
+                    continue
+                got[name] = t
+                setattr(q, name, t.data_ptr() if t.numel() else None)
+            q.flags = _native.DRAINAGE_DEVICE_POINTERS
+        self._check(self._lib.f3d_session_drainage(self._handle, C.byref(q), self._err, len(self._err)))
+        got.update(sinks=int(stats[0]), rounds=int(stats[1]), longest=int(stats[2]))
+        return got
+
+    def flow_directions(self, region=None):
+        """The D8 direction codes of drainage(), uint8 (rows, cols)."""
+        return self.drainage(region, direction=True, accumulation=False)["direction"]
+
+    def flow_accumulation(self, region=None):
+        """The flow accumulation of drainage(), uint32 (rows, cols)."""
+        return self.drainage(region, direction=False, accumulation=True)["accumulation"]
+
+    def basins(self, region=None):
+        """The basin labels of drainage(), uint32 (rows, cols): the linear index of each sample's sink."""
+        return self.drainage(region, direction=False, accumulation=False, basin=True)["basin"]
+
+    @staticmethod
+    def _threshold(threshold):
+        t = int(threshold)
+        if t != threshold or not 1 <= t <= 0xFFFFFFFF:
+            raise ValueError(f"threshold is an accumulation, an integer from 1 to 2^32 - 1, got {threshold}")
+        return t
+
+    STREAMS_FIRST_CAPACITY = 1 << 16  # records the host form of streams() makes room for before it knows the total
+
+    def streams(self, threshold, *, region=None, out=None):
+        """The stream network of the terrain (f3d_session_streams): every sample of ``region`` (samples, default the whole DEM)
+        that is no sink and has flow accumulation >= ``threshold`` gives one segment from its own lattice point to its
+        receiver's (which may lie outside the region), in row-major order of the region's samples.  Returns
+        ``{"segments": (N, 4) float32 (ax, az, bx, bz) in world x-z, "accumulation": (N,) uint32, "total": N}``.  The DEM is
+        routed by every call (drainage()); the host form makes room for STREAMS_FIRST_CAPACITY records and calls a second
+        time only for a larger network.  ``out=(segments, accumulation)``, torch tensors on the session's device of shape
+        (C, 4) float32 and (C,) int32 (``accumulation`` may be None), takes the device form: the first ``min(N, C)``
+        records are written there in one call, the values returned are views of them and ``"total"`` is N."""
+        t = self._threshold(threshold)
+        row0, col0, rows, cols = self._region(region)
+        total = C.c_uint64(0)
+        q = _native.StreamsDesc()
+        q.struct_size = C.sizeof(_native.StreamsDesc)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.threshold = t
+        q.total = C.addressof(total)
+        if out is not None:
+            seg, acc = out
+            if not _is_tensor(seg) or not seg.is_cuda or seg.ndim != 2 or seg.shape[1] != 4 or not seg.is_contiguous() or str(seg.dtype) != "torch.float32":
+                raise ValueError("out=(segments, accumulation): segments must be a contiguous float32 tensor (C, 4) on the session's device")
+            if acc is not None and (not _is_tensor(acc) or not acc.is_cuda or acc.ndim != 1 or acc.shape[0] != seg.shape[0] or
+                                    not acc.is_contiguous() or str(acc.dtype) != "torch.int32"):
+                raise ValueError("out=(segments, accumulation): accumulation must be a contiguous int32 tensor (C,) on the session's device, or None")
+            q.flags = _native.STREAMS_DEVICE_POINTERS
+            q.capacity = int(seg.shape[0])
+            q.segments = seg.data_ptr() if seg.shape[0] else None
+            q.accumulation = acc.data_ptr() if acc is not None and seg.shape[0] else None
+            self._check(self._lib.f3d_session_streams(self._handle, C.byref(q), self._err, len(self._err)))
+            n = min(int(total.value), int(seg.shape[0]))
+            return {"segments": seg[:n], "accumulation": None if acc is None else acc[:n], "total": int(total.value)}
+        room = max(1, min(rows * cols, self.STREAMS_FIRST_CAPACITY))
+        while True:
+            seg, acc = np.zeros((room, 4), np.float32), np.zeros(room, np.uint32)
+            q.capacity = room
+            q.segments, q.accumulation = seg.ctypes.data, acc.ctypes.data
+            self._check(self._lib.f3d_session_streams(self._handle, C.byref(q), self._err, len(self._err)))
+            n = int(total.value)
+            if n <= room:
+                return {"segments": seg[:n].copy(), "accumulation": acc[:n].copy(), "total": n}
+            room = n
+
+    def paint_streams(self, threshold, *, rgba=(0.1, 0.3, 0.8, 1.0), width=1.0, opacity=1.0, region=None, camera=None, **rearmable):
+        """paint() of the terrain's own stream network, without the segments leaving the GPU (f3d_session_paint_streams): the
+        segments streams() returns for ``threshold`` and ``region`` are emitted into the session's paint buffer and rasterised
+        into the drape as ``paint(segments, rgba, primitive="lines", width=width, opacity=opacity)`` paints them, bit for bit.
+        One call is one stroke style and one feature (confluences blend once); trunk streams are a second call with a
+        higher threshold.  ``rgba``: one linear colour with alpha (three numbers: alpha 1).  ``camera`` and the other values
+        as reaim() takes them; the render restarts at frame 0; a refused value leaves the session and the canvas as they
+        were.  Returns the number of segments painted."""
+        self._known("paint_streams", rearmable)
+        t = self._threshold(threshold)
+        row0, col0, rows, cols = self._region(region)
+        col = np.asarray(rgba, dtype=np.float32).reshape(-1)
+        if col.shape[0] not in (3, 4):
+            raise ValueError(f"rgba must be one colour of 3 or 4 numbers, got {np.shape(rgba)}")
+        if col.shape[0] == 3:
+            col = np.concatenate([col, np.ones(1, np.float32)])
+        width, opacity = float(width), float(opacity)
+        if not np.isfinite(width) or width < 0.0:
+            raise ValueError(f"width must be finite and >= 0 metres, got {width}")
+        if not 0.0 <= opacity <= 1.0:
+            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+        total = C.c_uint64(0)
+        q = _native.PaintStreamsDesc()
+        q.struct_size = C.sizeof(_native.PaintStreamsDesc)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        q.threshold = t
+        q.total = C.addressof(total)
+        q.rgba = (C.c_float * 4)(*(float(v) for v in col))
+        q.half_width = np.float32(width) * np.float32(0.5)
+        q.opacity = opacity
+        q.aim = self._aim(camera, rearmable)
+        self._update(self._lib.f3d_session_paint_streams, q, q.aim.arm, camera)
+        return int(total.value)
+
     def drape_image(self, region=None):
         """The session's drape as ``(rows, cols, 3)`` float32 linear RGB -- the values its binary16 texels hold -- after
         everything enqueued on the session, paint() included: what a composed map is saved with.  ``region`` is

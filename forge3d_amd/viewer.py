@@ -48,6 +48,7 @@ class ViewerHandle(OfflineTerrainViewer):
         self._overlay = None
         self._vector_layers = {}
         self._contours = None
+        self._streams = None
         self._vector_next_id = 1
         self._vector_canvas = None
 
@@ -315,13 +316,36 @@ class ViewerHandle(OfflineTerrainViewer):
         self._contours = None
         self._revision += 1
 
+    def enable_streams(self, threshold: int, *, width: float = 1.5, rgba=(0.1, 0.3, 0.8, 1.0), trunk_threshold: int = 0,
+                       trunk_width: float = 3.0) -> None:
+        """The stream network of the terrain as it is rendered -- every sample whose D8 flow accumulation reaches ``threshold``
+        samples, joined to its receiver --, painted on the GPU from the session's own tables (TerrainSession.paint_streams)
+        after the contour lines and before the vector layers.  ``width`` and ``trunk_width`` are stroke widths in canvas
+        texels; ``trunk_threshold`` > 0 paints the network of that higher accumulation a second time ``trunk_width`` wide (the
+        index contours' idiom).  ``rgba``: linear colour and alpha."""
+        width, trunk_width = float(width), float(trunk_width)
+        if int(threshold) != threshold or int(threshold) < 1 or int(trunk_threshold) != trunk_threshold or int(trunk_threshold) < 0:
+            raise ViewerError(f"stream thresholds are accumulations: threshold >= 1 and trunk_threshold >= 0, got {threshold} and {trunk_threshold}")
+        if not (np.isfinite(width) and width >= 0.0 and np.isfinite(trunk_width) and trunk_width >= 0.0):
+            raise ViewerError(f"stream widths must be finite and >= 0 texels, got {width} and {trunk_width}")
+        colour = np.asarray(rgba, np.float32).reshape(-1)
+        if colour.shape[0] not in (3, 4) or not np.all((colour >= 0.0) & (colour <= 1.0)):
+            raise ViewerError("stream rgba must be 3 or 4 numbers in [0, 1]")
+        self._streams = {"threshold": int(threshold), "width": width, "rgba": tuple(float(c) for c in colour),
+                         "trunk_threshold": int(trunk_threshold), "trunk_width": trunk_width}
+        self._revision += 1
+
+    def disable_streams(self) -> None:
+        self._streams = None
+        self._revision += 1
+
     def _painted(self) -> bool:
-        """Does the scene need a painted canvas: contour lines or vector layers?"""
-        return self._contours is not None or bool(self.vector_layers())
+        """Does the scene need a painted canvas: contour lines, streams or vector layers?"""
+        return self._contours is not None or self._streams is not None or bool(self.vector_layers())
 
     def _paint_layers(self, s, keywords) -> None:
-        """Drape ``s`` with the constant canvas unless an overlay image is there already, then paint the contour lines and,
-        over them, the layers."""
+        """Drape ``s`` with the constant canvas unless an overlay image is there already, then paint the contour lines, over
+        them the streams and, over those, the layers."""
         layers = self.vector_layers()
         if not self._painted():
             return
@@ -343,6 +367,11 @@ class ViewerHandle(OfflineTerrainViewer):
                 index = levels[k % c["index_every"] == 0]
                 if index.size:
                     s.paint_contours(index, rgba=c["rgba"], width=c["index_width"] * texel)
+        w = self._streams
+        if w is not None:
+            s.paint_streams(w["threshold"], rgba=w["rgba"], width=w["width"] * texel)
+            if w["trunk_threshold"] > 0:
+                s.paint_streams(w["trunk_threshold"], rgba=w["rgba"], width=w["trunk_width"] * texel)
         for layer in layers:
             s.paint(layer["xz"], layer["rgba"], layer["indices"], primitive=layer["primitive"], width=layer["texels"] * texel,
                     opacity=layer["opacity"], features=layer["features"])

@@ -43,7 +43,8 @@ extern "C" {
  *               which, with f3d_smoke_wait_fields_read, stays for this one revision as a shim over the thread's default
  *               context.  No struct changed: a caller built against version 3, 4 or 5 keeps working.
  *      since:   entry points with structs of their own are added without a bump and detected by their symbol (the session
- *               updates, queries, rasters, drape and paint; f3d_session_contours, f3d_session_paint_contours) */
+ *               updates, queries, rasters, drape and paint; f3d_session_contours, f3d_session_paint_contours; f3d_session_drainage,
+ *               f3d_session_streams, f3d_session_paint_streams) */
 #define F3D_ABI_VERSION 6u
 #define F3D_STATUS_OK 0
 #define F3D_STATUS_VALUE 1
@@ -887,6 +888,88 @@ typedef struct f3d_session_paint_contours_desc {
     f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
 } f3d_session_paint_contours_desc;
 int f3d_session_paint_contours(f3d_session *session, const f3d_session_paint_contours_desc *desc, char *err, size_t errlen);
+/* ---- drainage: flow directions, flow accumulation, basins and the stream network, on the device ---------------------------------
+ * Where water goes over the session's terrain as the leaf table holds it (heights f32(h * exaggeration), the y of a ground query).
+ * The rule is the opening comment of csrc/f3d_drainage.h (f32, one rounding per operation): D8 -- the eight neighbours in the order
+ * E, SE, S, SW, W, NW, N, NE = codes 0 .. 7 (+column east, +row south), slope = drop / run with run the spacing or, on a diagonal,
+ * sqrt(spacing_x^2 + spacing_z^2); the steepest positive slope wins, ties go to the lowest code; a sample without one is a sink,
+ * code 8 (pits, flats, the border's outlets).  Accumulation is the number of samples whose path passes through a sample, itself
+ * included; the basin of a sample is the linear index (row * dem_width + column) of the sink its path ends in.  No depressions
+ * are filled and no flats resolved.  THE WHOLE DEM IS ROUTED BY EVERY CALL, from the tables as they are (nothing is kept between
+ * calls; a re-terrain needs no invalidation): the region {row0, col0, rows, cols} of SAMPLES, as the visibility rasters', selects
+ * what is written.  The accumulation is summed by path doubling, floor(log2(longest path)) + 1 rounds of integer atomics: the
+ * results do not depend on the device's scheduling.  The scratch is the visibility rasters' buffer: 21 bytes a DEM sample, plus,
+ * in the host forms, what is written.
+ *
+ * f3d_session_drainage is a query (ordered on the session stream behind everything enqueued; the render goes on): direction
+ * (rows * cols u8), accumulation and basin (rows * cols u32 each), sample n = r * cols + c; each may be NULL.  stats (host memory,
+ * 3 u32) is always written: the DEM's sinks, the doubling rounds that had a live sample, the longest path in steps.  ms (host
+ * memory, 2 f64, or NULL): the host's clock to the device's end of the direction pass, then of the rounds.  With DEVICE_POINTERS
+ * the three planes are device memory (accumulation and basin 4-byte aligned).  There is no NO_WAIT: a counter crosses the bus
+ * after every round.  Refused with status 1, in this order: the struct size; unknown flags; reserved != 0; an empty region; a
+ * region that leaves the DEM; NULL stats; with DEVICE_POINTERS, a misaligned plane; a DEM of more than 2^31 samples (the live
+ * bit shares the pointer word; with it every DEM whose counts would not fit 32 bits).  Status 2: the scratch does not fit
+ * memory_budget_bytes.
+ *
+ * f3d_session_streams is a query: every sample of the region that is no sink and has accumulation >= threshold (>= 1) gives one
+ * segment from its own lattice point to its receiver's (which may lie outside the region), in row-major order of the region's
+ * samples.  It writes the first min(*total, capacity) records -- segments: 4 f32 (ax, az, bx, bz) in world x-z; accumulation:
+ * the sample's -- and always *total, so a call with capacity 0 sizes the next.  total is host memory; with DEVICE_POINTERS
+ * segments (16-byte aligned) and accumulation are device memory.  Refused with status 1, in this order: the struct size; unknown
+ * flags; reserved != 0; an empty region; a region that leaves the DEM; threshold 0; NULL total; capacity > 0 with NULL segments;
+ * with DEVICE_POINTERS, segments not 16-byte aligned; more than 2^31 samples.  Status 2 as above (the host form's records are
+ * sized by min(*total, capacity), not by the capacity).
+ *
+ * f3d_session_paint_streams is an update like f3d_session_paint_contours: the segments are emitted on the device straight into
+ * the session's paint buffer -- as `lines` of one feature with one colour, the bits f3d_session_paint builds for the same
+ * segments -- and rasterised by the same kernels; *total is the number painted (0: the drape keeps its bits).  Refused, in this
+ * order, the session and its drape unchanged: the struct size (its own, aim's, the re-arm's), peer halos, then as above through
+ * NULL total (status 1); a session without a drape; half_width negative or non-finite; opacity outside [0, 1]; more than 2^31
+ * samples; rgba outside [0, 1]; the region, widened by one sample, more than 65536 texels of the drape from the terrain's
+ * centre (status 3, as f3d_session_paint's reach); the re-arm's own refusals; and, after the count pass, more than
+ * F3D_PAINT_MAX_PRIMITIVES segments (status 1) or buffers beyond memory_budget_bytes (status 2).
+ * All three answer status 4 before any other check in a process without a HIP device.  No ABI version bump: detected by the
+ * symbols f3d_session_drainage, f3d_session_streams and f3d_session_paint_streams. */
+#define F3D_DRAINAGE_DEVICE_POINTERS 4u
+#define F3D_STREAMS_DEVICE_POINTERS 4u
+#define F3D_DRAINAGE_SINK 8u
+typedef struct f3d_session_drainage_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_drainage_desc) of the caller's header */
+    uint32_t flags;              /* F3D_DRAINAGE_DEVICE_POINTERS */
+    uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
+    uint8_t *direction;          /* rows * cols codes 0 .. 8, or NULL */
+    uint32_t *accumulation;      /* rows * cols, or NULL */
+    uint32_t *basin;             /* rows * cols, or NULL */
+    uint32_t *stats;             /* host memory, 3 u32: sinks, rounds, longest */
+    double *ms;                  /* host memory, 2 f64, or NULL */
+    uint32_t reserved;           /* 0 */
+} f3d_session_drainage_desc;
+int f3d_session_drainage(f3d_session *session, const f3d_session_drainage_desc *desc, char *err, size_t errlen);
+typedef struct f3d_session_streams_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_streams_desc) of the caller's header */
+    uint32_t flags;              /* F3D_STREAMS_DEVICE_POINTERS */
+    uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
+    uint32_t threshold;          /* >= 1: the accumulation from which a sample is a stream */
+    uint32_t reserved;           /* 0 */
+    float *segments;             /* capacity x 4 f32, or NULL */
+    uint32_t *accumulation;      /* capacity u32, or NULL */
+    uint64_t capacity;           /* records the outputs hold */
+    uint64_t *total;             /* host memory: the number of segments of the region */
+} f3d_session_streams_desc;
+int f3d_session_streams(f3d_session *session, const f3d_session_streams_desc *desc, char *err, size_t errlen);
+typedef struct f3d_session_paint_streams_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_paint_streams_desc) of the caller's header */
+    uint32_t flags;              /* none defined: 0 */
+    uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
+    uint32_t threshold;          /* >= 1 */
+    uint32_t reserved;           /* 0 */
+    uint64_t *total;             /* host memory: the number of segments painted */
+    float rgba[4];               /* [0, 1]: linear RGB reflectance and alpha of every segment */
+    float half_width;            /* metres: half the stroke width */
+    float opacity;               /* [0, 1] */
+    f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
+} f3d_session_paint_streams_desc;
+int f3d_session_paint_streams(f3d_session *session, const f3d_session_paint_streams_desc *desc, char *err, size_t errlen);
 /* The drape's texels as f32 RGB in host memory, after everything enqueued on the session: region = {row0, col0, rows, cols} (NULL:
  * the whole drape), rgb_out = rows x cols x 3 f32.  What a composed map is saved with.  Status 1: no drape, a region that leaves it. */
 int f3d_session_drape_read(f3d_session *session, const uint32_t region[4], float *rgb_out, char *err, size_t errlen);
