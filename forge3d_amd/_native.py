@@ -326,7 +326,19 @@ class PaintStreamsDesc(C.Structure):
     ]
 
 
-DRAINAGE_DEVICE_POINTERS = STREAMS_DEVICE_POINTERS = 4
+class FillDesc(C.Structure):
+    """f3d_session_fill_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_uint32),
+        ("row0", C.c_uint32), ("col0", C.c_uint32), ("rows", C.c_uint32), ("cols", C.c_uint32),
+        ("filled", C.c_void_p), ("depth", C.c_void_p), ("flat_distance", C.c_void_p),
+        ("stats", C.c_void_p), ("ms", C.c_void_p),
+        ("reserved", C.c_uint32),
+    ]
+
+
+DRAINAGE_DEVICE_POINTERS = STREAMS_DEVICE_POINTERS = FILL_DEVICE_POINTERS = 4
+DRAINAGE_FILL = STREAMS_FILL = 8  # F3D_DRAINAGE_FILL, F3D_STREAMS_FILL
 DRAINAGE_SINK = 8  # F3D_DRAINAGE_SINK
 
 
@@ -383,6 +395,7 @@ ABI = [
     ("f3d_session_drainage", C.c_int, [C.c_void_p, _P(DrainageDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_streams", C.c_int, [C.c_void_p, _P(StreamsDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_paint_streams", C.c_int, [C.c_void_p, _P(PaintStreamsDesc), C.c_char_p, C.c_size_t]),
+    ("f3d_session_fill", C.c_int, [C.c_void_p, _P(FillDesc), C.c_char_p, C.c_size_t]),
     ("f3d_session_drape_read", C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_void_p, C.c_char_p, C.c_size_t]),
     ("f3d_session_certificates", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("f3d_session_sky_blocks", C.c_int, [C.c_void_p, _P(C.c_uint32)]),
@@ -453,7 +466,7 @@ KERNEL_FLAGS = [
     # default is now 1.1 % FASTER, 8 690 -> 8 785 Msamples/s in one call, same image; profiles/r04_variant_ab.log)
 ]
 HIP_SOURCES = ["f3d_kernels.hip", "f3d_host.hip", "f3d_denoise.hip", "f3d_smoke.hip", "f3d_smoke_sim.hip", "f3d_composite.hip", "f3d_lbvh.hip", "f3d_bvh_refit.hip", "f3d_retable.hip", "f3d_wavefront.hip",
-               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip", "f3d_contour.hip", "f3d_drainage.hip"]
+               "f3d_aether_bake.hip", "f3d_aether_ref.hip", "f3d_paint.hip", "f3d_contour.hip", "f3d_drainage.hip", "f3d_fill.hip"]
 
 
 def source_digest() -> str:

@@ -96,6 +96,9 @@ struct DrainParams {
     uint32_t *stream_accumulation;  // capacity, or null
     PaintPrim *prims;          // capacity records, or null (then segments / stream_accumulation)
     float rgba[4];
+    // the filled form (f3d_fill.h: k_fill_direction reads them); null: unfilled
+    const float *fill_W;       // w * h words: the filled surface
+    const uint32_t *fill_T;    // w * h words: the distance across its flats
 };
 
 // (host, once per call)

@@ -74,6 +74,18 @@ hipError_t launch_drain_round(const DrainParams &p, hipStream_t stream);
 hipError_t launch_drain_write(const DrainParams &p, hipStream_t stream);
 hipError_t launch_stream_count(const DrainParams &p, void *scan_tmp, size_t scan_bytes, hipStream_t stream);
 hipError_t launch_stream_emit(const DrainParams &p, hipStream_t stream);
+// drainage through depressions (f3d_fill.h, f3d_fill.hip): z, W0 and every tile dirty (clears P.counters first); one round
+// P.round of the fill's relaxation over the tiles dirty in plane P.round & 1; T0 and the tiles that hold an undrained sample;
+// one round of the flats'; the direction pass over P.fill_W / P.fill_T in place of launch_drain_direction (clears P.counters
+// first); the filled samples and the largest T into the counters; the region out of the planes
+struct FillParams;
+hipError_t launch_fill_init(const FillParams &p, hipStream_t stream);
+hipError_t launch_fill_relax(const FillParams &p, hipStream_t stream);
+hipError_t launch_flat_init(const FillParams &p, hipStream_t stream);
+hipError_t launch_flat_relax(const FillParams &p, hipStream_t stream);
+hipError_t launch_fill_direction(const DrainParams &p, hipStream_t stream);
+hipError_t launch_fill_stats(const FillParams &p, hipStream_t stream);
+hipError_t launch_fill_write(const FillParams &p, hipStream_t stream);
 hipError_t launch_ray_batch(const RayBatchParams &p, hipStream_t stream);
 hipError_t launch_query(const QueryParams &p, hipStream_t stream);  // ray queries on a live session (f3d_query.h), 64 rays a workgroup
 hipError_t launch_raster(const RasterParams &p, hipStream_t stream);  // DEM visibility rasters (f3d_raster.h), 64 consecutive samples a workgroup

@@ -67,6 +67,31 @@ def _output(device, want, shape, dtype):
     return np.zeros(shape, dtype) if device is None else _torch.empty(shape, dtype=_TENSOR_BITS[dtype], device=device)
 
 
+class FilledRouting:
+    """``TerrainSession.filled``: the session's drainage calls with F3D_DRAINAGE_FILL set."""
+
+    def __init__(self, session):
+        self._session = session
+
+    def drainage(self, region=None, *, direction=True, accumulation=True, basin=False, out=None):
+        return self._session._drainage(region, direction, accumulation, basin, out, True)
+
+    def flow_directions(self, region=None):
+        return self.drainage(region, direction=True, accumulation=False)["direction"]
+
+    def flow_accumulation(self, region=None):
+        return self.drainage(region, direction=False, accumulation=True)["accumulation"]
+
+    def basins(self, region=None):
+        return self.drainage(region, direction=False, accumulation=False, basin=True)["basin"]
+
+    def streams(self, threshold, *, region=None, out=None):
+        return self._session._streams(threshold, region, out, True)
+
+    def paint_streams(self, threshold, **style):
+        return self._session.paint_streams(threshold, fill=True, **style)
+
+
 class TerrainSession:
     def __init__(self, heightmap, width, height, camera=None, *, row_begin=0, row_end=0, device=-1, stream=0,
                  memory_budget_bytes=0, kernel_variant=0, ext_reservoirs=(None, None), ext_stats=None, bands=0,
@@ -630,7 +655,8 @@ class TerrainSession:
         steepest positive float32 slope, ties to the lowest code; pits, flats and the border's outlets are sinks --, flow
         ``"accumulation"``, uint32: the samples whose path passes through a sample, itself included, and ``"basin"``, uint32: the
         linear index ``row * dem_width + col`` of the sink a sample drains to.  No depressions are filled and no flats
-        resolved.  The whole DEM is routed by every call, from the tables as reterrain() left them; ``region``
+        resolved here: ``session.filled.drainage(...)`` is the same call over the filled surface (fill()), where every path
+        reaches the border.  The whole DEM is routed by every call, from the tables as reterrain() left them; ``region``
         (``(row0, col0, rows, cols)`` in samples, default the whole DEM) selects what is returned, as arrays (rows, cols).
         Returns a dict of the planes asked for and always ``"sinks"`` (of the whole DEM), ``"rounds"`` (the path-doubling rounds
         the accumulation took: ``floor(log2(longest)) + 1``) and ``"longest"`` (the longest path, in steps).
@@ -639,6 +665,9 @@ class TerrainSession:
         counters.  The call always waits (a counter is read back after every round): ``wait=False`` is refused."""
         if not wait:
             raise ValueError("drainage() always waits: a counter crosses the bus after every doubling round, so there is no wait=False form")
+        return self._drainage(region, direction, accumulation, basin, out, False)
+
+    def _drainage(self, region, direction, accumulation, basin, out, fill):
         row0, col0, rows, cols = self._region(region)
         want = {"direction": bool(direction), "accumulation": bool(accumulation), "basin": bool(basin)}
         q = _native.DrainageDesc()
@@ -671,6 +700,8 @@ class TerrainSession:
                 got[name] = t
                 setattr(q, name, t.data_ptr() if t.numel() else None)
             q.flags = _native.DRAINAGE_DEVICE_POINTERS
+        if fill:
+            q.flags |= _native.DRAINAGE_FILL
         self._check(self._lib.f3d_session_drainage(self._handle, C.byref(q), self._err, len(self._err)))
         got.update(sinks=int(stats[0]), rounds=int(stats[1]), longest=int(stats[2]))
         return got
@@ -704,7 +735,11 @@ class TerrainSession:
         routed by every call (drainage()); the host form makes room for STREAMS_FIRST_CAPACITY records and calls a second
         time only for a larger network.  ``out=(segments, accumulation)``, torch tensors on the session's device of shape
         (C, 4) float32 and (C,) int32 (``accumulation`` may be None), takes the device form: the first ``min(N, C)``
-        records are written there in one call, the values returned are views of them and ``"total"`` is N."""
+        records are written there in one call, the values returned are views of them and ``"total"`` is N.
+        ``session.filled.streams(...)`` is the network over the filled surface."""
+        return self._streams(threshold, region, out, False)
+
+    def _streams(self, threshold, region, out, fill):
         t = self._threshold(threshold)
         row0, col0, rows, cols = self._region(region)
         total = C.c_uint64(0)
@@ -713,6 +748,7 @@ class TerrainSession:
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.threshold = t
         q.total = C.addressof(total)
+        q.flags = _native.STREAMS_FILL if fill else 0
         if out is not None:
             seg, acc = out
             if not _is_tensor(seg) or not seg.is_cuda or seg.ndim != 2 or seg.shape[1] != 4 or not seg.is_contiguous() or str(seg.dtype) != "torch.float32":
@@ -720,7 +756,7 @@ class TerrainSession:
             if acc is not None and (not _is_tensor(acc) or not acc.is_cuda or acc.ndim != 1 or acc.shape[0] != seg.shape[0] or
                                     not acc.is_contiguous() or str(acc.dtype) != "torch.int32"):
                 raise ValueError("out=(segments, accumulation): accumulation must be a contiguous int32 tensor (C,) on the session's device, or None")
-            q.flags = _native.STREAMS_DEVICE_POINTERS
+            q.flags |= _native.STREAMS_DEVICE_POINTERS
             q.capacity = int(seg.shape[0])
             q.segments = seg.data_ptr() if seg.shape[0] else None
             q.accumulation = acc.data_ptr() if acc is not None and seg.shape[0] else None
@@ -738,12 +774,13 @@ class TerrainSession:
                 return {"segments": seg[:n].copy(), "accumulation": acc[:n].copy(), "total": n}
             room = n
 
-    def paint_streams(self, threshold, *, rgba=(0.1, 0.3, 0.8, 1.0), width=1.0, opacity=1.0, region=None, camera=None, **rearmable):
+    def paint_streams(self, threshold, *, rgba=(0.1, 0.3, 0.8, 1.0), width=1.0, opacity=1.0, region=None, camera=None, fill=False, **rearmable):
         """paint() of the terrain's own stream network, without the segments leaving the GPU (f3d_session_paint_streams): the
         segments streams() returns for ``threshold`` and ``region`` are emitted into the session's paint buffer and rasterised
         into the drape as ``paint(segments, rgba, primitive="lines", width=width, opacity=opacity)`` paints them, bit for bit.
         One call is one stroke style and one feature (confluences blend once); trunk streams are a second call with a
-        higher threshold.  ``rgba``: one linear colour with alpha (three numbers: alpha 1).  ``camera`` and the other values
+        higher threshold.  ``fill=True`` paints the network over the filled surface (fill()): rivers that cross every lake and
+        flat and reach the border.  ``rgba``: one linear colour with alpha (three numbers: alpha 1).  ``camera`` and the other values
         as reaim() takes them; the render restarts at frame 0; a refused value leaves the session and the canvas as they
         were.  Returns the number of segments painted."""
         self._known("paint_streams", rearmable)
@@ -762,6 +799,7 @@ class TerrainSession:
         total = C.c_uint64(0)
         q = _native.PaintStreamsDesc()
         q.struct_size = C.sizeof(_native.PaintStreamsDesc)
+        q.flags = _native.STREAMS_FILL if fill else 0
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.threshold = t
         q.total = C.addressof(total)
@@ -771,6 +809,70 @@ class TerrainSession:
         q.aim = self._aim(camera, rearmable)
         self._update(self._lib.f3d_session_paint_streams, q, q.aim.arm, camera)
         return int(total.value)
+
+    # -- drainage through depressions: the filled surface, and the routing over it ----------------------------
+    _FILL_PLANES = (("filled", np.float32, "torch.float32"), ("depth", np.float32, "torch.float32"), ("flat_distance", np.uint32, "torch.int32"))
+
+    def fill(self, region=None, *, filled=True, depth=False, flat_distance=False, out=None):
+        """The terrain with its depressions filled to their spill points, computed on the GPU (f3d_session_fill): ``"filled"``,
+        float32: the surface W -- the heights on the DEM's border, elsewhere the least height over all paths to the border of
+        the highest sample on the path (what priority-flood computes) --, ``"depth"``, float32: ``W - z``, the water depth of
+        the lakes, and ``"flat_distance"``, uint32: the steps, within a level stretch of W, to where it drains (0 where a
+        neighbour is lower).  ``region`` and ``out`` (None, ``"device"``, or a dict of contiguous tensors (rows, cols) under the
+        planes' names: float32, float32, int32) as drainage() takes them.  Returns a dict of the planes asked for and always
+        ``"filled_samples"`` (of the whole DEM), ``"fill_rounds"``, ``"flat_rounds"`` (the rounds the two tiled relaxations
+        took; they depend on the device's schedule, the planes do not) and ``"largest_flat_distance"``.  The surface is
+        computed afresh by every call, from the tables as reterrain() left them."""
+        row0, col0, rows, cols = self._region(region)
+        want = {"filled": bool(filled), "depth": bool(depth), "flat_distance": bool(flat_distance)}
+        q = _native.FillDesc()
+        q.struct_size = C.sizeof(_native.FillDesc)
+        q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
+        stats = (C.c_uint32 * 4)()
+        q.stats = C.addressof(stats)
+        got = {}
+        if out is None:
+            for name, dtype, _ in self._FILL_PLANES:
+                if want[name]:
+                    got[name] = np.zeros((rows, cols), dtype)
+                    setattr(q, name, got[name].ctypes.data if got[name].size else None)
+        else:
+            import torch
+
+            given = {} if isinstance(out, str) else dict(out)
+            if (isinstance(out, str) and out != "device") or set(given) - set(want):
+                raise ValueError("out must be None, 'device' or a dict of tensors under 'filled', 'depth', 'flat_distance'")
+            device = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+            for name, _, tdtype in self._FILL_PLANES:
+                if name in given:
+                    t = given[name]
+                    if (not _is_tensor(t) or not t.is_cuda or tuple(t.shape) != (rows, cols) or not t.is_contiguous() or str(t.dtype) != tdtype):
+                        raise ValueError(f"out[{name!r}] must be a contiguous {tdtype} tensor ({rows}, {cols}) on the session's device")
+                elif want[name]:
+                    t = torch.empty((rows, cols), dtype=getattr(torch, tdtype.split(".")[1]), device=device)
+                else:
+                    continue
+                got[name] = t
+                setattr(q, name, t.data_ptr() if t.numel() else None)
+            q.flags = _native.FILL_DEVICE_POINTERS
+        self._check(self._lib.f3d_session_fill(self._handle, C.byref(q), self._err, len(self._err)))
+        got.update(filled_samples=int(stats[0]), fill_rounds=int(stats[1]), flat_rounds=int(stats[2]), largest_flat_distance=int(stats[3]))
+        return got
+
+    def filled_heights(self, region=None):
+        """The filled surface of fill(), float32 (rows, cols)."""
+        return self.fill(region)["filled"]
+
+    def lake_depth(self, region=None):
+        """The water depth of fill(), float32 (rows, cols): 0 outside the lakes."""
+        return self.fill(region, filled=False, depth=True)["depth"]
+
+    @property
+    def filled(self):
+        """The drainage calls over the FILLED surface (fill()): ``session.filled.drainage / flow_directions / flow_accumulation /
+        basins / streams / paint_streams`` take what the session's own methods take and route with F3D_DRAINAGE_FILL -- water
+        leaves every depression over its spill point, crosses every flat, and the only sinks are samples of the border."""
+        return FilledRouting(self)
 
     def drape_image(self, region=None):
         """The session's drape as ``(rows, cols, 3)`` float32 linear RGB -- the values its binary16 texels hold -- after

@@ -317,12 +317,13 @@ class ViewerHandle(OfflineTerrainViewer):
         self._revision += 1
 
     def enable_streams(self, threshold: int, *, width: float = 1.5, rgba=(0.1, 0.3, 0.8, 1.0), trunk_threshold: int = 0,
-                       trunk_width: float = 3.0) -> None:
+                       trunk_width: float = 3.0, fill: bool = False) -> None:
         """The stream network of the terrain as it is rendered -- every sample whose D8 flow accumulation reaches ``threshold``
         samples, joined to its receiver --, painted on the GPU from the session's own tables (TerrainSession.paint_streams)
         after the contour lines and before the vector layers.  ``width`` and ``trunk_width`` are stroke widths in canvas
         texels; ``trunk_threshold`` > 0 paints the network of that higher accumulation a second time ``trunk_width`` wide (the
-        index contours' idiom).  ``rgba``: linear colour and alpha."""
+        index contours' idiom).  ``rgba``: linear colour and alpha.  ``fill=True`` routes over the filled surface
+        (TerrainSession.fill): the rivers cross every lake and flat and reach the border."""
         width, trunk_width = float(width), float(trunk_width)
         if int(threshold) != threshold or int(threshold) < 1 or int(trunk_threshold) != trunk_threshold or int(trunk_threshold) < 0:
             raise ViewerError(f"stream thresholds are accumulations: threshold >= 1 and trunk_threshold >= 0, got {threshold} and {trunk_threshold}")
@@ -332,7 +333,7 @@ class ViewerHandle(OfflineTerrainViewer):
         if colour.shape[0] not in (3, 4) or not np.all((colour >= 0.0) & (colour <= 1.0)):
             raise ViewerError("stream rgba must be 3 or 4 numbers in [0, 1]")
         self._streams = {"threshold": int(threshold), "width": width, "rgba": tuple(float(c) for c in colour),
-                         "trunk_threshold": int(trunk_threshold), "trunk_width": trunk_width}
+                         "trunk_threshold": int(trunk_threshold), "trunk_width": trunk_width, "fill": bool(fill)}
         self._revision += 1
 
     def disable_streams(self) -> None:
@@ -369,9 +370,9 @@ class ViewerHandle(OfflineTerrainViewer):
                     s.paint_contours(index, rgba=c["rgba"], width=c["index_width"] * texel)
         w = self._streams
         if w is not None:
-            s.paint_streams(w["threshold"], rgba=w["rgba"], width=w["width"] * texel)
+            s.paint_streams(w["threshold"], rgba=w["rgba"], width=w["width"] * texel, fill=w["fill"])
             if w["trunk_threshold"] > 0:
-                s.paint_streams(w["trunk_threshold"], rgba=w["rgba"], width=w["trunk_width"] * texel)
+                s.paint_streams(w["trunk_threshold"], rgba=w["rgba"], width=w["trunk_width"] * texel, fill=w["fill"])
         for layer in layers:
             s.paint(layer["xz"], layer["rgba"], layer["indices"], primitive=layer["primitive"], width=layer["texels"] * texel,
                     opacity=layer["opacity"], features=layer["features"])

@@ -44,7 +44,7 @@ extern "C" {
  *               context.  No struct changed: a caller built against version 3, 4 or 5 keeps working.
  *      since:   entry points with structs of their own are added without a bump and detected by their symbol (the session
  *               updates, queries, rasters, drape and paint; f3d_session_contours, f3d_session_paint_contours; f3d_session_drainage,
- *               f3d_session_streams, f3d_session_paint_streams) */
+ *               f3d_session_streams, f3d_session_paint_streams; f3d_session_fill and the FILL flag of those three) */
 #define F3D_ABI_VERSION 6u
 #define F3D_STATUS_OK 0
 #define F3D_STATUS_VALUE 1
@@ -894,12 +894,12 @@ int f3d_session_paint_contours(f3d_session *session, const f3d_session_paint_con
  * E, SE, S, SW, W, NW, N, NE = codes 0 .. 7 (+column east, +row south), slope = drop / run with run the spacing or, on a diagonal,
  * sqrt(spacing_x^2 + spacing_z^2); the steepest positive slope wins, ties go to the lowest code; a sample without one is a sink,
  * code 8 (pits, flats, the border's outlets).  Accumulation is the number of samples whose path passes through a sample, itself
- * included; the basin of a sample is the linear index (row * dem_width + column) of the sink its path ends in.  No depressions
- * are filled and no flats resolved.  THE WHOLE DEM IS ROUTED BY EVERY CALL, from the tables as they are (nothing is kept between
+ * included; the basin of a sample is the linear index (row * dem_width + column) of the sink its path ends in.  Without the
+ * FILL flag (below) no depressions are filled and no flats resolved.  THE WHOLE DEM IS ROUTED BY EVERY CALL, from the tables as they are (nothing is kept between
  * calls; a re-terrain needs no invalidation): the region {row0, col0, rows, cols} of SAMPLES, as the visibility rasters', selects
  * what is written.  The accumulation is summed by path doubling, floor(log2(longest path)) + 1 rounds of integer atomics: the
- * results do not depend on the device's scheduling.  The scratch is the visibility rasters' buffer: 21 bytes a DEM sample, plus,
- * in the host forms, what is written.
+ * results do not depend on the device's scheduling.  The scratch is the visibility rasters' buffer: 21 bytes a DEM sample (33
+ * with FILL), plus, in the host forms, what is written.
  *
  * f3d_session_drainage is a query (ordered on the session stream behind everything enqueued; the render goes on): direction
  * (rows * cols u8), accumulation and basin (rows * cols u32 each), sample n = r * cols + c; each may be NULL.  stats (host memory,
@@ -929,13 +929,37 @@ int f3d_session_paint_contours(f3d_session *session, const f3d_session_paint_con
  * centre (status 3, as f3d_session_paint's reach); the re-arm's own refusals; and, after the count pass, more than
  * F3D_PAINT_MAX_PRIMITIVES segments (status 1) or buffers beyond memory_budget_bytes (status 2).
  * All three answer status 4 before any other check in a process without a HIP device.  No ABI version bump: detected by the
- * symbols f3d_session_drainage, f3d_session_streams and f3d_session_paint_streams. */
+ * symbols f3d_session_drainage, f3d_session_streams and f3d_session_paint_streams.
+ *
+ * HYDROLOGICALLY CONDITIONED ROUTING: F3D_DRAINAGE_FILL (= F3D_STREAMS_FILL, accepted in `flags` of all three descriptors; their
+ * members and every other bit's meaning are unchanged) routes over the FILLED surface instead, by the rule in the opening
+ * comment of csrc/f3d_fill.h.  A sample on the DEM's first or last row or column is an outlet.  The filled surface W is z on
+ * outlets and elsewhere the greatest solution of W(c) = max(z(c), min over the neighbours of W): the least height over all
+ * paths to an outlet of the highest sample on the path, what priority-flood computes.  The flat distance T is 0 on outlets and
+ * on samples with a strictly lower neighbour in W, elsewhere 1 + the least T among the neighbours of equal W.  The direction is
+ * D8 on W; a sample without a positive slope that is no outlet goes to the lowest code with a smaller W, or an equal W and a
+ * smaller T.  Every step lowers (W, T): the only sinks are outlets, every river reaches the border, the sinks' accumulations
+ * still sum to the DEM's samples.  Both surfaces are fixed points of monotone relaxations that only select among the input
+ * values: the bits do not depend on the device's scheduling.  Accumulation, basins, stats and the stream records keep their
+ * meaning over the new receivers.  Detected by the symbol f3d_session_fill.
+ *
+ * f3d_session_fill is a query like f3d_session_drainage: of the region's samples, filled (W, f32), depth (W - z, one f32
+ * subtraction: the lakes' water depth) and flat_distance (T, u32), rows * cols each, any of them NULL.  stats (host memory,
+ * 4 u32, or NULL): the DEM's samples with W > z, the rounds of the fill pass, the rounds of the flat pass, the largest T.  ms
+ * (host memory, 2 f64, or NULL): the host's clock to the device's end of the fill pass, then of the flat pass.  With
+ * DEVICE_POINTERS the three planes are device memory, 4-byte aligned.  The scratch is 12 bytes a DEM sample plus, in the host
+ * form, what is written.  Refused with status 1, in this order: the struct size; unknown flags; reserved != 0; an empty region;
+ * a region that leaves the DEM; with DEVICE_POINTERS, a misaligned plane; a DEM of more than 2^31 samples.  Status 2: the
+ * scratch does not fit memory_budget_bytes.  Status 4 before any other check in a process without a HIP device. */
 #define F3D_DRAINAGE_DEVICE_POINTERS 4u
 #define F3D_STREAMS_DEVICE_POINTERS 4u
+#define F3D_DRAINAGE_FILL 8u
+#define F3D_STREAMS_FILL 8u
+#define F3D_FILL_DEVICE_POINTERS 4u
 #define F3D_DRAINAGE_SINK 8u
 typedef struct f3d_session_drainage_desc {
     uint32_t struct_size;        /* = sizeof(f3d_session_drainage_desc) of the caller's header */
-    uint32_t flags;              /* F3D_DRAINAGE_DEVICE_POINTERS */
+    uint32_t flags;              /* F3D_DRAINAGE_DEVICE_POINTERS, F3D_DRAINAGE_FILL */
     uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
     uint8_t *direction;          /* rows * cols codes 0 .. 8, or NULL */
     uint32_t *accumulation;      /* rows * cols, or NULL */
@@ -947,7 +971,7 @@ typedef struct f3d_session_drainage_desc {
 int f3d_session_drainage(f3d_session *session, const f3d_session_drainage_desc *desc, char *err, size_t errlen);
 typedef struct f3d_session_streams_desc {
     uint32_t struct_size;        /* = sizeof(f3d_session_streams_desc) of the caller's header */
-    uint32_t flags;              /* F3D_STREAMS_DEVICE_POINTERS */
+    uint32_t flags;              /* F3D_STREAMS_DEVICE_POINTERS, F3D_STREAMS_FILL */
     uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
     uint32_t threshold;          /* >= 1: the accumulation from which a sample is a stream */
     uint32_t reserved;           /* 0 */
@@ -959,7 +983,7 @@ typedef struct f3d_session_streams_desc {
 int f3d_session_streams(f3d_session *session, const f3d_session_streams_desc *desc, char *err, size_t errlen);
 typedef struct f3d_session_paint_streams_desc {
     uint32_t struct_size;        /* = sizeof(f3d_session_paint_streams_desc) of the caller's header */
-    uint32_t flags;              /* none defined: 0 */
+    uint32_t flags;              /* F3D_STREAMS_FILL */
     uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
     uint32_t threshold;          /* >= 1 */
     uint32_t reserved;           /* 0 */
@@ -970,6 +994,18 @@ typedef struct f3d_session_paint_streams_desc {
     f3d_session_reaim_desc aim;  /* camera + everything a re-arm takes, same meaning */
 } f3d_session_paint_streams_desc;
 int f3d_session_paint_streams(f3d_session *session, const f3d_session_paint_streams_desc *desc, char *err, size_t errlen);
+typedef struct f3d_session_fill_desc {
+    uint32_t struct_size;        /* = sizeof(f3d_session_fill_desc) of the caller's header */
+    uint32_t flags;              /* F3D_FILL_DEVICE_POINTERS */
+    uint32_t row0, col0, rows, cols; /* the region, in DEM samples */
+    float *filled;               /* rows * cols f32: the filled surface W, or NULL */
+    float *depth;                /* rows * cols f32: W - z, or NULL */
+    uint32_t *flat_distance;     /* rows * cols u32: T, or NULL */
+    uint32_t *stats;             /* host memory, 4 u32: filled samples, fill rounds, flat rounds, largest T; or NULL */
+    double *ms;                  /* host memory, 2 f64, or NULL */
+    uint32_t reserved;           /* 0 */
+} f3d_session_fill_desc;
+int f3d_session_fill(f3d_session *session, const f3d_session_fill_desc *desc, char *err, size_t errlen);
 /* The drape's texels as f32 RGB in host memory, after everything enqueued on the session: region = {row0, col0, rows, cols} (NULL:
  * the whole drape), rgb_out = rows x cols x 3 f32.  What a composed map is saved with.  Status 1: no drape, a region that leaves it. */
 int f3d_session_drape_read(f3d_session *session, const uint32_t region[4], float *rgb_out, char *err, size_t errlen);
