@@ -331,7 +331,10 @@ __device__ float sun_transmittance(const SmokeParams &P, const SmokeBox &box, V3
               (1.0f + soot * P.st.soot_absorption) * P.shadow_step;
         if (od > 8.0f) break;
     }
-    return f_clamp(exp_det(-od), 0.0f, 1.0f);
+    // f32::clamp hands a NaN back (render.rs:315) where fminf / fmaxf would drop it: a march that crossed a NaN density leaves
+    // the pixel's colour NaN, which to_u8 writes as 0, and its alpha untouched (tests/test_smoke.py, the non-finite case)
+    const float tr = exp_det(-od);
+    return tr != tr ? tr : f_clamp(tr, 0.0f, 1.0f);
 }
 
 __device__ __forceinline__ V3 mix3(V3 a, V3 b, float t) {

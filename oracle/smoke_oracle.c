@@ -11,9 +11,20 @@
  *   sample_scalar / lerp / hash01          src/smoke/sampling.rs:1-34, :88-103
  *   grid_coord_from_world / bounds_*       src/smoke/types.rs:375-397
  *   SmokeRenderSettings::validate          src/smoke/types.rs:271-316
- * PARITY PIN: the reference (Rust) cannot be built here and ships no golden image of this path; the oracle is
- * pinned by the reference's own unit tests restated as known-answer properties (render.rs:420-592) in
- * tests/test_smoke.py -- "parity pinned by KAT properties only" (DESIGN.md).  Arithmetic: IEEE f32, no
+ * PARITY PIN: the reference (Rust) cannot be built here and ships no golden image of this path.  Three things pin the
+ * oracle: the reference's own unit tests restated as known-answer properties (render.rs:420-592) and the vectors of its
+ * NumPy helpers for the primitives (tests/test_smoke.py); and, for everything between the primitives and the pixel -- the
+ * march loop, the extinction and albedo chain, smoke_color, the light terms, the self-shadow march's own extinction, the
+ * cut-offs, the un-premultiply and the tone map -- an independent float64 statement of both renders written from
+ * render.rs (tests/smoke_march_reference.py).  This file's float march (smoke_oracle_hook_march, below) equals that
+ * statement to within 1.2 ... 110 eps32 of a channel's largest value on thirteen sets.  A 1 % change of any constant of the
+ * statement's table makes at least one set fail, except six whose change provably cannot move a compared pixel; each is
+ * derived in tests/test_smoke_march_reference_host.py (EXEMPT).
+ * NaN: clampf keeps one as f32::clamp does, fmaxf / fminf drop one as f32::max / min do, to_u8 writes one as 0 as `as u8`
+ * does -- Rust's semantics at every site.  The HIP kernel follows them only where a NaN DENSITY can reach (dropped by the
+ * ray's max(., 0), kept by the self-shadow transmittance's clamp, tests/test_smoke.py); its other clamps drop a NaN, so for
+ * a NaN in soot, humidity, temperature, emission or age this file and the kernel are NOT bit-identical, and nothing tests
+ * that (the domain's setters refuse non-finite fields).  Arithmetic: IEEE f32, no
  * contraction (-ffp-contract=off), glam's scalar Vec3 operation order; e^x is the fixed polynomial exp_det
  * shared (restated, not included) with the HIP kernel, powf(d, 1.5) = d * sqrtf(d): both within 2 ulp of the
  * libm calls Rust makes, which the 8-bit outputs absorb. */
@@ -53,7 +64,7 @@ static v3 normalize_or_zero(v3 a) { /* glam Vec3::normalize_or_zero */
     return (v3){0.0f, 0.0f, 0.0f};
 }
 static v3 normalize(v3 a) { return v3_scale(a, 1.0f / sqrtf(v3_dot(a, a))); }
-static float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+static float clampf(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); } /* f32::clamp: a NaN stays (f32::max / min drop it) */
 static float lerpf(float a, float b, float t) { return a + (b - a) * t; }
 
 /* e^x, fixed polynomial (cephes expf scheme), every operation spelled */
@@ -93,7 +104,8 @@ static size_t vidx(const uint32_t d[3], uint32_t x, uint32_t y, uint32_t z) { re
 static float sample_scalar(const float *f, const uint32_t d[3], const float p[3]) {
     float x = clampf(p[0], 0.0f, (float)(d[0] - 1)), y = clampf(p[1], 0.0f, (float)(d[1] - 1)),
           z = clampf(p[2], 0.0f, (float)(d[2] - 1));
-    uint32_t x0 = (uint32_t)floorf(x), y0 = (uint32_t)floorf(y), z0 = (uint32_t)floorf(z);
+    /* (`as usize` of a NaN is 0: a NaN coordinate, which clampf keeps, must not become an index) */
+    uint32_t x0 = x != x ? 0u : (uint32_t)floorf(x), y0 = y != y ? 0u : (uint32_t)floorf(y), z0 = z != z ? 0u : (uint32_t)floorf(z);
     uint32_t x1 = x0 + 1 < d[0] - 1 ? x0 + 1 : d[0] - 1, y1 = y0 + 1 < d[1] - 1 ? y0 + 1 : d[1] - 1,
              z1 = z0 + 1 < d[2] - 1 ? z0 + 1 : d[2] - 1;
     float fx = x - (float)x0, fy = y - (float)y0, fz = z - (float)z0;
@@ -167,7 +179,7 @@ static v3 smoke_color(render_sample s, const smoke_settings *st) {
     return mix_vec3(c, (v3){0.95f, 0.62f, 0.28f}, heat * 0.07f);
 }
 
-static uint8_t to_u8(float v) { return (uint8_t)(clampf(v, 0.0f, 1.0f) * 255.0f + 0.5f); }
+static uint8_t to_u8(float v) { return v != v ? 0 : (uint8_t)(clampf(v, 0.0f, 1.0f) * 255.0f + 0.5f); } /* `as u8` of a NaN is 0 */
 
 float smoke_oracle_sun_transmittance(const smoke_volume *v, const float start_[3], const float sun_[3], float step,
                                      uint32_t steps, const smoke_settings *st) {
@@ -189,8 +201,12 @@ float smoke_oracle_sun_transmittance(const smoke_volume *v, const float start_[3
     return clampf(exp_det(-od), 0.0f, 1.0f);
 }
 
-static void march_ray_rgba(const smoke_volume *v, v3 origin, v3 dir, float t0, float t1, uint32_t seed, float step,
-                           float shadow_step, v3 sun, const smoke_settings *st, uint8_t out[4]) {
+/* the float march: straight colour after the tone map, alpha, the ray's transmittance and its step count, before the
+ * four to_u8 calls (what smoke_oracle_hook_march hands to tests/smoke_march_reference.py) */
+typedef struct { v3 mapped; float alpha, transmittance; uint32_t steps; } march_result;
+
+static march_result march_ray(const smoke_volume *v, v3 origin, v3 dir, float t0, float t1, uint32_t seed, float step,
+                              float shadow_step, v3 sun, const smoke_settings *st) {
     float jitter = (hash01(seed) - 0.5f) * st->jitter_strength * step;
     float t = fmaxf(t0 + jitter, 0.0f), transmittance = 1.0f;
     v3 rgb = {0.0f, 0.0f, 0.0f};
@@ -235,10 +251,23 @@ static void march_ray_rgba(const smoke_volume *v, v3 origin, v3 dir, float t0, f
     float alpha = clampf(1.0f - transmittance, 0.0f, 1.0f);
     v3 straight = alpha > 1.0e-5f ? (v3){rgb.x / alpha, rgb.y / alpha, rgb.z / alpha} : rgb;
     v3 e = v3_scale(straight, st->exposure);
-    out[0] = to_u8(e.x / (1.0f + e.x));
-    out[1] = to_u8(e.y / (1.0f + e.y));
-    out[2] = to_u8(e.z / (1.0f + e.z));
-    out[3] = to_u8(alpha);
+    return (march_result){{e.x / (1.0f + e.x), e.y / (1.0f + e.y), e.z / (1.0f + e.z)}, alpha, transmittance, steps};
+}
+
+/* one pixel of either render: the bytes (out, may be null) and / or the floats behind them (fout, 6 per pixel, may be null) */
+static void march_ray_rgba(const smoke_volume *v, v3 origin, v3 dir, float t0, float t1, uint32_t seed, float step,
+                           float shadow_step, v3 sun, const smoke_settings *st, uint8_t *out, float *fout) {
+    march_result r = march_ray(v, origin, dir, t0, t1, seed, step, shadow_step, sun, st);
+    if (out) {
+        out[0] = to_u8(r.mapped.x);
+        out[1] = to_u8(r.mapped.y);
+        out[2] = to_u8(r.mapped.z);
+        out[3] = to_u8(r.alpha);
+    }
+    if (fout) {
+        fout[0] = r.mapped.x, fout[1] = r.mapped.y, fout[2] = r.mapped.z;
+        fout[3] = r.alpha, fout[4] = r.transmittance, fout[5] = (float)r.steps;
+    }
 }
 
 static int fail(char *err, size_t n, const char *msg) {
@@ -282,9 +311,18 @@ static void step_sizes(const smoke_volume *v, const smoke_settings *st, float *s
     *shadow_step = st->shadow_step_size > 0.0f ? st->shadow_step_size : *step * 2.0f;
 }
 
-int smoke_oracle_raymarch_rgba(const smoke_volume *v, uint32_t width, uint32_t height, const float cam[3],
-                               const float target_[3], const float up_[3], float fovy_deg, const float sun_[3],
-                               const smoke_settings *st, uint8_t *out, char *err, size_t errlen) {
+static void clear_outputs(uint8_t *out, float *fout, size_t pixels) { /* a ray that misses the box: zero bytes, transmittance 1 */
+    if (out) memset(out, 0, pixels * 4);
+    if (fout)
+        for (size_t i = 0; i < pixels; i++) {
+            memset(fout + 6 * i, 0, 6 * sizeof(float));
+            fout[6 * i + 4] = 1.0f;
+        }
+}
+
+static int raymarch_perspective(const smoke_volume *v, uint32_t width, uint32_t height, const float cam[3],
+                                const float target_[3], const float up_[3], float fovy_deg, const float sun_[3],
+                                const smoke_settings *st, uint8_t *out, float *fout, char *err, size_t errlen) {
     if (validate_settings(st, err, errlen)) return 1;
     if (width == 0 || height == 0) return fail(err, errlen, "width and height must be >= 1");
     if (!isfinite(fovy_deg) || fovy_deg <= 0.0f || fovy_deg >= 179.0f)
@@ -303,7 +341,7 @@ int smoke_oracle_raymarch_rgba(const smoke_volume *v, uint32_t width, uint32_t h
     float tan_half = tanf((fovy_deg * (3.14159265358979323846f / 180.0f)) * 0.5f);
     float aspect = (float)width / (float)height;
     v3 bmin = bounds_min(v), bmax = bounds_max(v);
-    memset(out, 0, (size_t)width * height * 4);
+    clear_outputs(out, fout, (size_t)width * height);
 #pragma omp parallel for schedule(dynamic, 4)
     for (long y = 0; y < (long)height; y++)
         for (uint32_t x = 0; x < width; x++) {
@@ -314,14 +352,21 @@ int smoke_oracle_raymarch_rgba(const smoke_volume *v, uint32_t width, uint32_t h
             if (!ray_box_intersection(eye, dir, bmin, bmax, &t0, &t1)) continue;
             t0 = fmaxf(t0, 0.0f);
             uint32_t seed = x * 73856093u + (uint32_t)y * 19349663u + v->frame_index;
-            march_ray_rgba(v, eye, dir, t0, t1, seed, step, shadow_step, sun, st, out + ((size_t)y * width + x) * 4);
+            size_t pixel = (size_t)y * width + x;
+            march_ray_rgba(v, eye, dir, t0, t1, seed, step, shadow_step, sun, st, out ? out + pixel * 4 : 0, fout ? fout + pixel * 6 : 0);
         }
     return 0;
 }
 
-int smoke_oracle_raymarch_projection_rgba(const smoke_volume *v, uint32_t width, uint32_t height, const float view_[3],
-                                          const float sun_[3], const smoke_settings *st, uint8_t *out, char *err,
-                                          size_t errlen) {
+int smoke_oracle_raymarch_rgba(const smoke_volume *v, uint32_t width, uint32_t height, const float cam[3],
+                               const float target_[3], const float up_[3], float fovy_deg, const float sun_[3],
+                               const smoke_settings *st, uint8_t *out, char *err, size_t errlen) {
+    return raymarch_perspective(v, width, height, cam, target_, up_, fovy_deg, sun_, st, out, 0, err, errlen);
+}
+
+static int raymarch_projection(const smoke_volume *v, uint32_t width, uint32_t height, const float view_[3],
+                               const float sun_[3], const smoke_settings *st, uint8_t *out, float *fout, char *err,
+                               size_t errlen) {
     if (validate_settings(st, err, errlen)) return 1;
     if (width == 0 || height == 0) return fail(err, errlen, "width and height must be >= 1");
     v3 dir = normalize_or_zero((v3){view_[0], view_[1], view_[2]});
@@ -333,7 +378,7 @@ int smoke_oracle_raymarch_projection_rgba(const smoke_volume *v, uint32_t width,
     v3 bmin = bounds_min(v), bmax = bounds_max(v);
     v3 ext = v3_sub(bmax, bmin);
     float diagonal = fmaxf(sqrtf(v3_dot(ext, ext)), step * 2.0f);
-    memset(out, 0, (size_t)width * height * 4);
+    clear_outputs(out, fout, (size_t)width * height);
 #pragma omp parallel for schedule(dynamic, 4)
     for (long py = 0; py < (long)height; py++) {
         float fz = ((float)py + 0.5f) / (float)height;
@@ -347,10 +392,27 @@ int smoke_oracle_raymarch_projection_rgba(const smoke_volume *v, uint32_t width,
             if (!ray_box_intersection(origin, dir, bmin, bmax, &t0, &t1)) continue;
             t0 = fmaxf(t0, 0.0f);
             uint32_t seed = px * 73856093u + (uint32_t)py * 19349663u + v->frame_index + 0x9e3779b9u;
-            march_ray_rgba(v, origin, dir, t0, t1, seed, step, shadow_step, sun, st, out + ((size_t)py * width + px) * 4);
+            size_t pixel = (size_t)py * width + px;
+            march_ray_rgba(v, origin, dir, t0, t1, seed, step, shadow_step, sun, st, out ? out + pixel * 4 : 0, fout ? fout + pixel * 6 : 0);
         }
     }
     return 0;
+}
+
+int smoke_oracle_raymarch_projection_rgba(const smoke_volume *v, uint32_t width, uint32_t height, const float view_[3],
+                                          const float sun_[3], const smoke_settings *st, uint8_t *out, char *err,
+                                          size_t errlen) {
+    return raymarch_projection(v, width, height, view_, sun_, st, out, 0, err, errlen);
+}
+
+/* The float march of either render (tests/test_smoke_march_reference_host.py): the arguments of both, `projection` chooses;
+ * out holds 6 floats per pixel -- straight tone-mapped r, g, b, alpha, transmittance, step count -- and a ray that misses
+ * the box leaves 0, 0, 0, 0, 1, 0. */
+int smoke_oracle_hook_march(const smoke_volume *v, uint32_t width, uint32_t height, int32_t projection, const float cam[3],
+                            const float target_[3], const float up_[3], float fovy_deg, const float view_[3],
+                            const float sun_[3], const smoke_settings *st, float *out, char *err, size_t errlen) {
+    if (projection) return raymarch_projection(v, width, height, view_, sun_, st, 0, out, err, errlen);
+    return raymarch_perspective(v, width, height, cam, target_, up_, fovy_deg, sun_, st, 0, out, err, errlen);
 }
 
 /* ---- hooks onto the marcher's primitives (tests/test_smoke.py: pinned against vectors written by the REFERENCE's own NumPy

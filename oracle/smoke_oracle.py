@@ -119,6 +119,24 @@ def render_projection_rgba(fields, width, height, view_direction=(0.0, -1.0, 0.0
     return out
 
 
+def hook_march(fields, width, height, projection=False, camera_pos=(0.0, 0.0, -1.0), target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), fovy_deg=45.0,
+               view_direction=(0.0, -1.0, 0.0), sun_direction=(0.4, 0.8, -0.2), voxel_size=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0),
+               frame_index=0, **settings):
+    """The float march behind render_rgba (projection=False) or render_projection_rgba: per pixel the straight tone-mapped
+    rgb (height, width, 3), alpha, the ray's transmittance (float32) and its step count (int64), before the 8-bit rounding."""
+    v, keep = _volume(fields, voxel_size, origin, frame_index)
+    s = _settings(**settings)
+    out = np.zeros((height, width, 6), np.float32)
+    err = C.create_string_buffer(256)
+    f3 = lambda t: (C.c_float * 3)(*t)  # noqa: E731
+    rc = lib().smoke_oracle_hook_march(C.byref(v), C.c_uint32(width), C.c_uint32(height), C.c_int32(1 if projection else 0), f3(camera_pos),
+                                       f3(target), f3(up), C.c_float(fovy_deg), f3(view_direction), f3(sun_direction), C.byref(s),
+                                       C.c_void_p(out.ctypes.data), err, C.c_size_t(len(err)))
+    if rc != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(rgb=out[..., :3].copy(), alpha=out[..., 3].copy(), transmittance=out[..., 4].copy(), steps=out[..., 5].astype(np.int64))
+
+
 def sun_transmittance(fields, start, sun_dir, step, steps, voxel_size=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), **settings):
     v, keep = _volume(fields, voxel_size, origin, 0)
     s = _settings(**settings)

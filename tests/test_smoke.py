@@ -1,7 +1,8 @@
 """Smoke ray-marcher: the oracle against the reference's own unit tests restated as
-known-answer properties (src/smoke/render.rs:420-592, tests/test_smoke.py:54-76 of the reference) -- the only
-pins this path has: the reference ships no golden image for it and cannot be built here -- and, `-m gpu`, the HIP
-kernel against the oracle bit for bit (integer RGBA8 outputs)."""
+known-answer properties (src/smoke/render.rs:420-592, tests/test_smoke.py:54-76 of the reference) -- the reference
+ships no golden image for this path and cannot be built here; what lies between the primitives and the pixel is pinned
+by the float64 statement of a ray, tests/test_smoke_march_reference_host.py -- and, `-m gpu`, the HIP kernel against
+the oracle bit for bit (integer RGBA8 outputs)."""
 from __future__ import annotations
 
 import numpy as np
@@ -250,6 +251,126 @@ def test_clipping_against_the_smoke_box_changes_nothing(case):
         assert np.array_equal(got_p, want_p)
     if density.any():
         assert int(want[..., 3].max()) > 0
+
+
+def _forms(monkeypatch, form):
+    monkeypatch.delenv("F3D_SMOKE_MARCH", raising=False)
+    monkeypatch.delenv("F3D_SMOKE_SHADOW_SLOTS", raising=False)
+    if form == "single":
+        monkeypatch.setenv("F3D_SMOKE_MARCH", form)
+    elif form == "deferred-short-list":
+        monkeypatch.setenv("F3D_SMOKE_SHADOW_SLOTS", "3072")
+
+
+@pytest.mark.gpu
+def test_fuzz_slice_matches_the_oracle_bit_for_bit(monkeypatch):
+    """Seeds 1 ... 40 of tools/gpu_fuzz_smoke.py (tests/smoke_march_cases.py, `case`): random volumes under 40^3, cameras inside and
+    outside, axis-parallel rays and suns, awkward voxel sizes and far origins, images under 70 x 50, through both renders, every
+    byte; every fifth seed with a self-shadow list of two chunks, as the tool does.  What this drives is the machinery around
+    the reference's loop: the empty-space map, the smoke box with its rounding margins, div_known against plain division, the
+    in_smoke shortcut and the chunked deferred list."""
+    from forge3d_amd import smoke
+    import smoke_march_cases
+
+    smoky, bad = 0, []
+    for seed in range(1, 41):
+        fields, vs, og, pos, target, up, fov, sun, view, st, w, h, frame = smoke_march_cases.case(seed)
+        if seed % 5 == 0:
+            monkeypatch.setenv("F3D_SMOKE_SHADOW_SLOTS", "2048")
+        else:
+            monkeypatch.delenv("F3D_SMOKE_SHADOW_SLOTS", raising=False)
+        dom = _domain(fields, vs, og, frame)
+        settings = smoke.SmokeRenderSettings(**st)
+        got = dom.render_rgba(w, h, pos, target, up=up, fovy_deg=fov, sun_direction=sun, settings=settings)
+        want = smoke_oracle.render_rgba(fields, w, h, pos, target, up=up, fovy_deg=fov, sun_direction=sun, voxel_size=vs, origin=og, frame_index=frame, **st)
+        got_p = dom.render_projection_rgba(w, h, view, sun, settings=settings)
+        want_p = smoke_oracle.render_projection_rgba(fields, w, h, view, sun, voxel_size=vs, origin=og, frame_index=frame, **st)
+        smoky += int(want[..., 3].any()) + int(want_p[..., 3].any())
+        if not np.array_equal(got, want):
+            bad.append((seed, "perspective", int((got != want).any(-1).sum())))
+        if not np.array_equal(got_p, want_p):
+            bad.append((seed, "projection", int((got_p != want_p).any(-1).sum())))
+    assert not bad, bad
+    assert smoky >= 40, f"{smoky} of 80 images show smoke"  # 41 with NumPy's PCG64 streams of today: a margin of one image
+
+
+def _both_renders(name, size=None):
+    """(device call, oracle call) pairs of a set of tests/smoke_march_cases.py under both renders, at its own or another size."""
+    import smoke_march_cases
+
+    s = smoke_march_cases.reference_sets()[name]
+    w, h = size or s["size"]
+    cam = s["camera"] or smoke_march_cases.reference_sets()["plume"]["camera"]
+    view = s["view"] or (0.2, -1.0, 0.1)
+    geo = dict(voxel_size=s["voxel_size"], origin=s["origin"], frame_index=s["frame_index"])
+    return s, geo, [
+        (lambda dom, st: dom.render_rgba(w, h, settings=st, sun_direction=s["sun"], **cam),
+         lambda fields: smoke_oracle.render_rgba(fields, w, h, sun_direction=s["sun"], **cam, **geo, **s["settings"])),
+        (lambda dom, st: dom.render_projection_rgba(w, h, view, s["sun"], settings=st),
+         lambda fields: smoke_oracle.render_projection_rgba(fields, w, h, view, s["sun"], **geo, **s["settings"])),
+    ]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["deferred", "deferred-short-list", "single"])
+@pytest.mark.parametrize("name,size", [("thin", None), ("awkward-voxel", None), ("tiny-voxel", None), ("plume", (1, 1)), ("plume", (7, 9)), ("plume", (9, 8))],
+                         ids=["thin", "awkward-voxel", "tiny-voxel", "plume-1x1", "plume-7x9", "plume-9x8"])
+def test_edge_volumes_and_images_match_the_oracle_bit_for_bit(name, size, form, monkeypatch):
+    """Shapes the other cases do not have: a grid axis of 2 under a 5 x 3 image; a voxel size one ulp under 2, which
+    div_known_divisor refuses, so that make_tap's plain-division branch makes every pixel (and a voxel of 1 / 3); voxel edges of 5e-5 ... 7e-5 under the default
+    settings, where the step is the floor 0.75 * 1e-4 and not 0.75 of a voxel (the host code's own copy of that floor); images of one
+    pixel, smaller than an 8 x 8 tile in both directions, and one pixel over a tile."""
+    from forge3d_amd import smoke
+
+    _forms(monkeypatch, form)
+    s, geo, renders = _both_renders(name, size)
+    if name == "awkward-voxel":
+        import ctypes
+
+        from emul import emul
+
+        emul.lib().emul_div_known_divisor.argtypes = [ctypes.c_float]
+        assert emul.lib().emul_div_known_divisor(s["voxel_size"][0]) == 0  # refused: the plain division
+    dom = _domain(s["fields"], s["voxel_size"], s["origin"], s["frame_index"])
+    st = smoke.SmokeRenderSettings(**s["settings"])
+    shown = 0
+    for device, oracle_render in renders:
+        want = oracle_render(s["fields"])
+        shown += int(want[..., 3].any())
+        assert np.array_equal(device(dom, st), want)
+    assert shown == 2  # both renders show smoke, the single pixel of the 1 x 1 images included
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["deferred", "deferred-short-list", "single"])
+def test_non_finite_and_signed_density_renders_what_the_reference_would(form, monkeypatch):
+    """One NaN voxel, one negative voxel and one -0.0 voxel in the density of `plume` (the setters refuse non-finite fields, as
+    the reference's do, so they are written into the domain's array the way a solver gone wrong would leave them), both
+    renders, every byte against the oracle.  What the reference does with them (render.rs): f32::max drops a NaN, so a ray
+    step whose tap touches the NaN voxel has density max(NaN, 0) = 0 and is skipped; a self-shadow march that crosses it has
+    optical depth NaN, and f32::clamp hands a NaN back, so that step's light and with it the pixel's colour are NaN, which
+    `as u8` writes as 0 -- black under an alpha that the NaN never touched.  k_smoke_pack marks every tap of the NaN voxel and
+    of the negative one (`d != 0`), so none of this is skipped; the -0.0 voxel is not marked and adds -0 where it is read."""
+    from forge3d_amd import smoke
+
+    _forms(monkeypatch, form)
+    s, geo, renders = _both_renders("plume")
+    fields = {k: v.copy() for k, v in s["fields"].items()}
+    d = fields["density"]
+    z, y, x = np.meshgrid(*(np.arange(n) for n in d.shape), indexing="ij")
+    order = np.argsort(np.where((d > 0.2) & (d < 0.5), y - 0.5 * z, -np.inf), axis=None)[::-1]  # the plume's skin towards sun and camera
+    nan_at, neg_at, zero_at = (np.unravel_index(order[i], d.shape) for i in (0, 3, 6))
+    clean = [oracle_render(fields) for _, oracle_render in renders]
+    dom = _domain(fields, s["voxel_size"], s["origin"], s["frame_index"])
+    d[nan_at], d[neg_at], d[zero_at] = np.nan, -0.8, -0.0
+    dom.density = d
+    st = smoke.SmokeRenderSettings(**s["settings"])
+    for (device, oracle_render), before in zip(renders, clean):
+        want = oracle_render(fields)
+        black = (want[..., :3] == 0).all(-1) & (want[..., 3] > 0)
+        assert black.sum() >= 4 and not ((before[..., :3] == 0).all(-1) & (before[..., 3] > 0)).any()  # the NaN reached pixels
+        assert (want != before).any(-1).sum() > black.sum()  # and so did the negative voxel
+        assert np.array_equal(device(dom, st), want)
 
 
 @pytest.mark.gpu
