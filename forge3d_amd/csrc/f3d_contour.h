@@ -171,6 +171,16 @@ F3D_HD PaintPrim contour_prim(const float rgba[4], float ax, float az, float bx,
     return p;
 }
 
+#if defined(__HIPCC__)
+// ... and how the emit kernels (f3d_contour.hip, f3d_drainage.hip) write it: a record is 80 bytes in a buffer aligned to 256,
+// five 16-byte stores.
+__device__ __forceinline__ void contour_prim_store(PaintPrim *dst, const PaintPrim &p) {
+    uint4 words[kPaintPrimWords / 4u];
+    __builtin_memcpy(words, &p, sizeof p);
+    for (uint32_t k = 0u; k < kPaintPrimWords / 4u; k++) ((uint4 *)dst)[k] = words[k];
+}
+#endif
+
 // lane -> cell of block (bx, bz); false: outside the region
 F3D_HD bool contour_lane_cell(const ContourParams &P, uint32_t bx, uint32_t bz, uint32_t lane, uint32_t &cx, uint32_t &cz) {
     cx = (bx << 3) + (lane & 7u);

@@ -48,12 +48,7 @@ __global__ __launch_bounds__(64) void k_contour_emit(const ContourParams P) {
     if (P.prims) {
         contour_lane_emit(P, L.cx, L.cz, L.rec, L.l0, L.l1, at, [&](uint64_t i, float ax, float az, float bx, float bz, uint32_t) {
             if (i >= P.capacity) return;
-            const PaintPrim p = contour_prim(P.rgba, ax, az, bx, bz);
-            // (a record is 80 bytes in a buffer aligned to 256: five 16-byte stores)
-            uint4 words[kPaintPrimWords / 4u];
-            __builtin_memcpy(words, &p, sizeof p);
-            uint4 *dst = (uint4 *)(P.prims + i);
-            for (uint32_t k = 0u; k < kPaintPrimWords / 4u; k++) dst[k] = words[k];
+            contour_prim_store(P.prims + i, contour_prim(P.rgba, ax, az, bx, bz));
         });
     } else {
         contour_lane_emit(P, L.cx, L.cz, L.rec, L.l0, L.l1, at, [&](uint64_t i, float ax, float az, float bx, float bz, uint32_t k) {

@@ -83,12 +83,7 @@ __global__ __launch_bounds__(64) void k_stream_emit(const DrainParams P) {
     float ax, az, bx, bz;
     stream_segment(P.terrain, i, j, code, ax, az, bx, bz);
     if (P.prims) {
-        const PaintPrim p = contour_prim(P.rgba, ax, az, bx, bz);
-        // (a record is 80 bytes in a buffer aligned to 256: five 16-byte stores)
-        uint4 words[kPaintPrimWords / 4u];
-        __builtin_memcpy(words, &p, sizeof p);
-        uint4 *dst = (uint4 *)(P.prims + at);
-        for (uint32_t k = 0u; k < kPaintPrimWords / 4u; k++) dst[k] = words[k];
+        contour_prim_store(P.prims + at, contour_prim(P.rgba, ax, az, bx, bz));
     } else {
         if (P.segments) *(float4 *)(P.segments + 4u * at) = float4{ax, az, bx, bz};
         if (P.stream_accumulation) P.stream_accumulation[at] = accumulation;

@@ -4,9 +4,15 @@
 // paint is a re-aim over a changed canvas.  Behind it the read-back of the drape (f3d_session_drape_read).
 #pragma once
 
+#include "f3d_scratch_carve.h"
+
 namespace {
 
-size_t paint_align(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+// The stroke of a call -- f3d_session_paint's and the derived paints' (f3d_host_derived.h).
+void paint_stroke(float half_width, float opacity) {
+    if (!std::isfinite(half_width) || half_width < 0.0f) fail(F3D_STATUS_VALUE, "paint half_width must be finite and >= 0 metres, got %g", (double)half_width);
+    if (!(opacity >= 0.0f && opacity <= 1.0f)) fail(F3D_STATUS_VALUE, "paint opacity must lie in [0, 1], got %g", (double)opacity);
+}
 
 // The canvas and the style of a call: everything of PaintParams but the records and the binning's storage.
 PaintParams paint_params(const f3d_session &s, uint32_t kind, float half_width, float opacity) {
@@ -37,17 +43,17 @@ PaintStorage paint_records(f3d_session &s, PaintParams &P, uint32_t n) {
     f3d_session::Paint &B = s.paint;
     size_t scan_bytes = 0;
     hip_check(paint_scan_bytes(n, &scan_bytes), "paint scan storage");
-    const size_t rec_bytes = paint_align((size_t)n * sizeof(PaintPrim)), word_bytes = paint_align(((size_t)n + 1u) * sizeof(uint64_t));
+    Carver c;
+    const PaintRecordsLayout L = paint_records_layout(c, n, sizeof(PaintPrim), scan_bytes);
     // (the old buffer may still be read by the previous call's kernels: see the second buffer in paint_run)
-    grow_scratch(s, B.prims, B.prim_bytes, rec_bytes + 2u * word_bytes + 256u + paint_align(scan_bytes), "paint",
-                 "the primitive records and the binning's counters bring", "paint primitives");
+    grow_scratch(s, B.prims, B.prim_bytes, c.at, "paint", "the primitive records and the binning's counters bring", "paint primitives");
     char *base = (char *)B.prims;
-    P.prims = (const PaintPrim *)base;
+    P.prims = (const PaintPrim *)(base + L.records);
     P.prim_count = n;
-    P.counts = (uint64_t *)(base + rec_bytes);
-    P.offsets = (const uint64_t *)(base + rec_bytes + word_bytes);
-    P.run_count = (uint32_t *)(base + rec_bytes + 2u * word_bytes);
-    return {base + rec_bytes + 2u * word_bytes + 256u, scan_bytes};
+    P.counts = (uint64_t *)(base + L.counts);
+    P.offsets = (const uint64_t *)(base + L.offsets);
+    P.run_count = (uint32_t *)(base + L.run_count);
+    return {base + L.scan, scan_bytes};
 }
 
 // The records are on the device (or on their way, on the session stream): count, bin, paint, with the timing marks.
@@ -75,19 +81,19 @@ void paint_run(f3d_session &s, PaintParams &P, const PaintStorage &at) {
         P.key_count = (uint32_t)total;
         size_t sort_bytes = 0;
         hip_check(paint_sort_bytes(P.key_count, tiles, &sort_bytes), "paint sort storage");
-        const size_t key_bytes = paint_align((size_t)total * sizeof(uint64_t)), run_bytes = paint_align((size_t)std::min<uint64_t>(total, tiles) * sizeof(uint32_t));
+        Carver c;
+        const PaintKeysLayout L = paint_keys_layout(c, (size_t)total, (size_t)std::min<uint64_t>(total, tiles), sort_bytes);
         // (a refusal here leaves the first buffer as it has just grown -- gpu_resource_bytes may have risen -- and everything a
         // render or fingerprint reads as it was.  grow_scratch gives the old buffer back at once although the previous call's k_paint
         // may still read it: Ledger::free ends in the pool's device-wide wait or in hipFree, which waits too; a free path that did
         // not would have to wait for the session stream here first)
-        grow_scratch(s, B.keys, B.key_bytes, 2u * key_bytes + run_bytes + paint_align(sort_bytes), "paint",
-                     "the (tile, primitive) keys and the storage of their sort bring", "paint keys");
+        grow_scratch(s, B.keys, B.key_bytes, c.at, "paint", "the (tile, primitive) keys and the storage of their sort bring", "paint keys");
         char *kb = (char *)B.keys;
-        P.keys = (uint64_t *)kb;
-        P.sorted = (const uint64_t *)(kb + key_bytes);
-        P.runs = (uint32_t *)(kb + 2u * key_bytes);
+        P.keys = (uint64_t *)(kb + L.keys);
+        P.sorted = (const uint64_t *)(kb + L.sorted);
+        P.runs = (uint32_t *)(kb + L.runs);
         hip_check(hipEventRecord(B.mark[2], s.stream), "paint timing event");  // (behind the wait for the key count)
-        hip_check(launch_paint_bin(P, tiles, kb + 2u * key_bytes + run_bytes, sort_bytes, s.stream), "paint binning kernels");
+        hip_check(launch_paint_bin(P, tiles, kb + L.sort, sort_bytes, s.stream), "paint binning kernels");
         hip_check(hipEventRecord(B.mark[3], s.stream), "paint timing event");
         uint32_t runs = 0u;
         hip_check(hipMemcpyAsync(&runs, P.run_count, sizeof runs, hipMemcpyDeviceToHost, s.stream), "paint tile count");
@@ -120,9 +126,7 @@ void session_paint(f3d_session &s, const f3d_session_paint_desc &q) {
     for (uint32_t i = 0; i < q.index_count; i++)
         if (q.indices[i] >= q.vertex_count)
             fail(F3D_STATUS_VALUE, "paint index %u is %u, the call has %u vertices", i, q.indices[i], q.vertex_count);
-    if (!std::isfinite(q.half_width) || q.half_width < 0.0f)
-        fail(F3D_STATUS_VALUE, "paint half_width must be finite and >= 0 metres, got %g", (double)q.half_width);
-    if (!(q.opacity >= 0.0f && q.opacity <= 1.0f)) fail(F3D_STATUS_VALUE, "paint opacity must lie in [0, 1], got %g", (double)q.opacity);
+    paint_stroke(q.half_width, q.opacity);
     // (REACH of f3d_paint.h: the coordinates the binning's slacks are sized for)
     const float reach = kPaintMaxReach * paint_ramp(s.params.terrain.spacing_x, D.record.scale_x, s.params.terrain.spacing_z, D.record.scale_z);
     u.validate([&] {

@@ -41,7 +41,7 @@ def _form(x, wait, noun, plural, device=None):
     if _torch is None:
         import torch  # (only for callers who hand tensors in)
 
-        _TENSOR_BITS.update({np.float32: torch.float32, np.uint32: torch.int32, np.uint64: torch.int64})
+        _TENSOR_BITS.update({np.float32: torch.float32, np.uint32: torch.int32, np.uint64: torch.int64, np.uint8: torch.uint8})
         _torch = torch
     return x.device if device is None else device
 
@@ -65,6 +65,24 @@ def _output(device, want, shape, dtype):
     if not want:
         return None
     return np.zeros(shape, dtype) if device is None else _torch.empty(shape, dtype=_TENSOR_BITS[dtype], device=device)
+
+
+def _stroke(rgba, width, opacity):
+    """The stroke of a paint call, checked: ``(one RGBA colour as float32 -- three numbers: alpha 1; None for ``rgba=None``, the
+    caller's own colours --, the float32 half-width, the opacity)``."""
+    col = None
+    if rgba is not None:
+        col = np.asarray(rgba, dtype=np.float32).reshape(-1)
+        if col.shape[0] not in (3, 4):
+            raise ValueError(f"rgba must be one colour of 3 or 4 numbers, got {np.shape(rgba)}")
+        if col.shape[0] == 3:
+            col = np.concatenate([col, np.ones(1, np.float32)])
+    width, opacity = float(width), float(opacity)
+    if not np.isfinite(width) or width < 0.0:
+        raise ValueError(f"width must be finite and >= 0 metres, got {width}")
+    if not 0.0 <= opacity <= 1.0:
+        raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+    return col, np.float32(width) * np.float32(0.5), opacity
 
 
 class FilledRouting:
@@ -438,11 +456,7 @@ class TerrainSession:
             raise ValueError(f"a paint call takes at most {_native.PAINT_MAX_PRIMITIVES} primitives, got {idx.size // per}")
         if int(idx.max()) >= n:
             raise ValueError(f"index {int(idx.max())} is out of range: the call has {n} vertices")
-        width, opacity = float(width), float(opacity)
-        if not np.isfinite(width) or width < 0.0:
-            raise ValueError(f"width must be finite and >= 0 metres, got {width}")
-        if not 0.0 <= opacity <= 1.0:
-            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+        _, half_width, opacity = _stroke(None, width, opacity)
         ids = None
         if features is not None:
             raw = np.asarray(features)
@@ -456,10 +470,64 @@ class TerrainSession:
         q.xz, q.rgba = pts.ctypes.data, col.ctypes.data
         q.feature = ids.ctypes.data if ids is not None else None
         q.indices, q.index_count = idx.ctypes.data, idx.size
-        q.half_width = np.float32(width) * np.float32(0.5)
-        q.opacity = opacity
+        q.half_width, q.opacity = half_width, opacity
         q.aim = self._aim(camera, rearmable)
         self._update(self._lib.f3d_session_paint, q, q.aim.arm, camera)  # (pts, col, ids and idx live until here)
+
+    def _paint_segments(self, entry, q, rgba, width, opacity, camera, rearmable):
+        """What paint_contours() and paint_streams() share behind their own arguments: the stroke, the common tail of the two
+        descriptors (total, rgba, half_width, opacity, aim), the update.  Returns the number of segments painted."""
+        col, half_width, opacity = _stroke(rgba, width, opacity)
+        total = C.c_uint64(0)
+        q.struct_size = C.sizeof(q)
+        q.total = C.addressof(total)
+        q.rgba = (C.c_float * 4)(*(float(v) for v in col))
+        q.half_width, q.opacity = half_width, opacity
+        q.aim = self._aim(camera, rearmable)
+        self._update(getattr(self._lib, entry), q, q.aim.arm, camera)  # (what q points to lives in the caller until here)
+        return int(total.value)
+
+    def _records_out(self, entry, q, total, out, second):
+        """The device form of a call that returns records, ``out=(segments, second)``: the two tensors checked, the capacity and
+        the pointers in ``q``, the call, and the views of what was written -- ``segments`` and ``second``'s name their keys."""
+        seg, word = out
+        if not _is_tensor(seg) or not seg.is_cuda or seg.ndim != 2 or seg.shape[1] != 4 or not seg.is_contiguous() or str(seg.dtype) != "torch.float32":
+            raise ValueError(f"out=(segments, {second}): segments must be a contiguous float32 tensor (C, 4) on the session's device")
+        if word is not None and (not _is_tensor(word) or not word.is_cuda or word.ndim != 1 or word.shape[0] != seg.shape[0] or
+                                 not word.is_contiguous() or str(word.dtype) != "torch.int32"):
+            raise ValueError(f"out=(segments, {second}): {second} must be a contiguous int32 tensor (C,) on the session's device, or None")
+        q.capacity = int(seg.shape[0])
+        q.segments = seg.data_ptr() if seg.shape[0] else None
+        setattr(q, second, word.data_ptr() if word is not None and seg.shape[0] else None)
+        self._check(getattr(self._lib, entry)(self._handle, C.byref(q), self._err, len(self._err)))
+        n = min(int(total.value), int(seg.shape[0]))
+        return {"segments": seg[:n], second: None if word is None else word[:n], "total": int(total.value)}
+
+    def _planes(self, q, table, want, out, shape, device_pointers):
+        """The planes of a call by name.  ``table``: ``(member of q, NumPy dtype, tensor dtype)`` a plane; ``want``: name -> asked
+        for; ``out``: None -- NumPy arrays --, ``"device"`` -- tensors on the session's device -- or a dict of the caller's own
+        tensors under the planes' names, checked against ``shape``, the others allocated.  Sets the members of ``q`` (an empty
+        plane stays null) and, for tensors, the flag ``device_pointers``; returns name -> plane for the planes of the call."""
+        given, device = {}, None
+        if out is not None:
+            given = {} if isinstance(out, str) else dict(out)
+            if (isinstance(out, str) and out != "device") or set(given) - set(want):
+                raise ValueError("out must be None, 'device' or a dict of tensors under " + ", ".join(repr(name) for name, _, _ in table))
+            device = _form(None, True, None, None, device=f"cuda:{self._device}" if self._device >= 0 else "cuda")
+            q.flags |= device_pointers
+        got = {}
+        for name, dtype, tensor_dtype in table:
+            if name in given:
+                t = given[name]
+                if not _is_tensor(t) or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous() or str(t.dtype) != tensor_dtype:
+                    raise ValueError(f"out[{name!r}] must be a contiguous {tensor_dtype} tensor ({shape[0]}, {shape[1]}) on the session's device")
+            elif want[name]:
+                t = _output(device, True, shape, dtype)
+            else:
+                continue
+            got[name] = t
+            setattr(q, name, None if shape[0] * shape[1] == 0 else t.ctypes.data if device is None else t.data_ptr())
+        return got
 
     def paint_stats(self):
         """``None`` before the first paint(), else the last call's device times in ms (``count_ms``: count pass and scan,
@@ -529,21 +597,10 @@ class TerrainSession:
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.levels, q.level_count = lv.ctypes.data, lv.size
         q.total = C.addressof(total)
-        entry = self._lib.f3d_session_contours
         if out is not None:
-            seg, idx = out
-            if not _is_tensor(seg) or not seg.is_cuda or seg.ndim != 2 or seg.shape[1] != 4 or not seg.is_contiguous() or str(seg.dtype) != "torch.float32":
-                raise ValueError("out=(segments, level_index): segments must be a contiguous float32 tensor (C, 4) on the session's device")
-            if idx is not None and (not _is_tensor(idx) or not idx.is_cuda or idx.ndim != 1 or idx.shape[0] != seg.shape[0] or
-                                    not idx.is_contiguous() or str(idx.dtype) != "torch.int32"):
-                raise ValueError("out=(segments, level_index): level_index must be a contiguous int32 tensor (C,) on the session's device, or None")
             q.flags = _native.CONTOUR_DEVICE_POINTERS
-            q.capacity = int(seg.shape[0])
-            q.segments = seg.data_ptr() if seg.shape[0] else None
-            q.level_index = idx.data_ptr() if idx is not None and seg.shape[0] else None
-            self._check(entry(self._handle, C.byref(q), self._err, len(self._err)))
-            n = min(int(total.value), int(seg.shape[0]))
-            return {"segments": seg[:n], "level_index": None if idx is None else idx[:n], "levels": lv, "total": int(total.value)}
+            return dict(self._records_out("f3d_session_contours", q, total, out, "level_index"), levels=lv)
+        entry = self._lib.f3d_session_contours
         self._check(entry(self._handle, C.byref(q), self._err, len(self._err)))  # (null outputs: the total)
         n = int(total.value)
         seg, idx = np.zeros((n, 4), np.float32), np.zeros(n, np.uint32)
@@ -620,28 +677,10 @@ class TerrainSession:
         self._known("paint_contours", rearmable)
         lv = self._contour_levels(levels, interval, base)
         row0, col0, rows, cols = self._cell_region(region)
-        col = np.asarray(rgba, dtype=np.float32).reshape(-1)
-        if col.shape[0] not in (3, 4):
-            raise ValueError(f"rgba must be one colour of 3 or 4 numbers, got {np.shape(rgba)}")
-        if col.shape[0] == 3:
-            col = np.concatenate([col, np.ones(1, np.float32)])
-        width, opacity = float(width), float(opacity)
-        if not np.isfinite(width) or width < 0.0:
-            raise ValueError(f"width must be finite and >= 0 metres, got {width}")
-        if not 0.0 <= opacity <= 1.0:
-            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
-        total = C.c_uint64(0)
         q = _native.PaintContoursDesc()
-        q.struct_size = C.sizeof(_native.PaintContoursDesc)
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.levels, q.level_count = lv.ctypes.data, lv.size
-        q.total = C.addressof(total)
-        q.rgba = (C.c_float * 4)(*(float(v) for v in col))
-        q.half_width = np.float32(width) * np.float32(0.5)
-        q.opacity = opacity
-        q.aim = self._aim(camera, rearmable)
-        self._update(self._lib.f3d_session_paint_contours, q, q.aim.arm, camera)  # (lv lives until here)
-        return int(total.value)
+        return self._paint_segments("f3d_session_paint_contours", q, rgba, width, opacity, camera, rearmable)  # (lv lives until here)
 
     # -- drainage: flow directions, accumulation, basins, the stream network, on the GPU -------------------
     DRAINAGE_SINK = _native.DRAINAGE_SINK
@@ -675,31 +714,7 @@ class TerrainSession:
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         stats = (C.c_uint32 * 3)()
         q.stats = C.addressof(stats)
-        got = {}
-        if out is None:
-            for name, dtype, _ in self._DRAINAGE_PLANES:
-                if want[name]:
-                    got[name] = np.zeros((rows, cols), dtype)
-                    setattr(q, name, got[name].ctypes.data if got[name].size else None)
-        else:
-            import torch
-
-            given = {} if isinstance(out, str) else dict(out)
-            if (isinstance(out, str) and out != "device") or set(given) - set(want):
-                raise ValueError("out must be None, 'device' or a dict of tensors under 'direction', 'accumulation', 'basin'")
-            device = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
-            for name, _, tdtype in self._DRAINAGE_PLANES:
-                if name in given:
-                    t = given[name]
-                    if (not _is_tensor(t) or not t.is_cuda or tuple(t.shape) != (rows, cols) or not t.is_contiguous() or str(t.dtype) != tdtype):
-                        raise ValueError(f"out[{name!r}] must be a contiguous {tdtype} tensor ({rows}, {cols}) on the session's device")
-                elif want[name]:
-                    t = torch.empty((rows, cols), dtype=getattr(torch, tdtype.split(".")[1]), device=device)
-                else:
-                    continue
-                got[name] = t
-                setattr(q, name, t.data_ptr() if t.numel() else None)
-            q.flags = _native.DRAINAGE_DEVICE_POINTERS
+        got = self._planes(q, self._DRAINAGE_PLANES, want, out, (rows, cols), _native.DRAINAGE_DEVICE_POINTERS)
         if fill:
             q.flags |= _native.DRAINAGE_FILL
         self._check(self._lib.f3d_session_drainage(self._handle, C.byref(q), self._err, len(self._err)))
@@ -750,19 +765,8 @@ class TerrainSession:
         q.total = C.addressof(total)
         q.flags = _native.STREAMS_FILL if fill else 0
         if out is not None:
-            seg, acc = out
-            if not _is_tensor(seg) or not seg.is_cuda or seg.ndim != 2 or seg.shape[1] != 4 or not seg.is_contiguous() or str(seg.dtype) != "torch.float32":
-                raise ValueError("out=(segments, accumulation): segments must be a contiguous float32 tensor (C, 4) on the session's device")
-            if acc is not None and (not _is_tensor(acc) or not acc.is_cuda or acc.ndim != 1 or acc.shape[0] != seg.shape[0] or
-                                    not acc.is_contiguous() or str(acc.dtype) != "torch.int32"):
-                raise ValueError("out=(segments, accumulation): accumulation must be a contiguous int32 tensor (C,) on the session's device, or None")
             q.flags |= _native.STREAMS_DEVICE_POINTERS
-            q.capacity = int(seg.shape[0])
-            q.segments = seg.data_ptr() if seg.shape[0] else None
-            q.accumulation = acc.data_ptr() if acc is not None and seg.shape[0] else None
-            self._check(self._lib.f3d_session_streams(self._handle, C.byref(q), self._err, len(self._err)))
-            n = min(int(total.value), int(seg.shape[0]))
-            return {"segments": seg[:n], "accumulation": None if acc is None else acc[:n], "total": int(total.value)}
+            return self._records_out("f3d_session_streams", q, total, out, "accumulation")
         room = max(1, min(rows * cols, self.STREAMS_FIRST_CAPACITY))
         while True:
             seg, acc = np.zeros((room, 4), np.float32), np.zeros(room, np.uint32)
@@ -786,29 +790,11 @@ class TerrainSession:
         self._known("paint_streams", rearmable)
         t = self._threshold(threshold)
         row0, col0, rows, cols = self._region(region)
-        col = np.asarray(rgba, dtype=np.float32).reshape(-1)
-        if col.shape[0] not in (3, 4):
-            raise ValueError(f"rgba must be one colour of 3 or 4 numbers, got {np.shape(rgba)}")
-        if col.shape[0] == 3:
-            col = np.concatenate([col, np.ones(1, np.float32)])
-        width, opacity = float(width), float(opacity)
-        if not np.isfinite(width) or width < 0.0:
-            raise ValueError(f"width must be finite and >= 0 metres, got {width}")
-        if not 0.0 <= opacity <= 1.0:
-            raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
-        total = C.c_uint64(0)
         q = _native.PaintStreamsDesc()
-        q.struct_size = C.sizeof(_native.PaintStreamsDesc)
         q.flags = _native.STREAMS_FILL if fill else 0
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         q.threshold = t
-        q.total = C.addressof(total)
-        q.rgba = (C.c_float * 4)(*(float(v) for v in col))
-        q.half_width = np.float32(width) * np.float32(0.5)
-        q.opacity = opacity
-        q.aim = self._aim(camera, rearmable)
-        self._update(self._lib.f3d_session_paint_streams, q, q.aim.arm, camera)
-        return int(total.value)
+        return self._paint_segments("f3d_session_paint_streams", q, rgba, width, opacity, camera, rearmable)
 
     # -- drainage through depressions: the filled surface, and the routing over it ----------------------------
     _FILL_PLANES = (("filled", np.float32, "torch.float32"), ("depth", np.float32, "torch.float32"), ("flat_distance", np.uint32, "torch.int32"))
@@ -830,31 +816,7 @@ class TerrainSession:
         q.row0, q.col0, q.rows, q.cols = row0, col0, rows, cols
         stats = (C.c_uint32 * 4)()
         q.stats = C.addressof(stats)
-        got = {}
-        if out is None:
-            for name, dtype, _ in self._FILL_PLANES:
-                if want[name]:
-                    got[name] = np.zeros((rows, cols), dtype)
-                    setattr(q, name, got[name].ctypes.data if got[name].size else None)
-        else:
-            import torch
-
-            given = {} if isinstance(out, str) else dict(out)
-            if (isinstance(out, str) and out != "device") or set(given) - set(want):
-                raise ValueError("out must be None, 'device' or a dict of tensors under 'filled', 'depth', 'flat_distance'")
-            device = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
-            for name, _, tdtype in self._FILL_PLANES:
-                if name in given:
-                    t = given[name]
-                    if (not _is_tensor(t) or not t.is_cuda or tuple(t.shape) != (rows, cols) or not t.is_contiguous() or str(t.dtype) != tdtype):
-                        raise ValueError(f"out[{name!r}] must be a contiguous {tdtype} tensor ({rows}, {cols}) on the session's device")
-                elif want[name]:
-                    t = torch.empty((rows, cols), dtype=getattr(torch, tdtype.split(".")[1]), device=device)
-                else:
-                    continue
-                got[name] = t
-                setattr(q, name, t.data_ptr() if t.numel() else None)
-            q.flags = _native.FILL_DEVICE_POINTERS
+        got = self._planes(q, self._FILL_PLANES, want, out, (rows, cols), _native.FILL_DEVICE_POINTERS)
         self._check(self._lib.f3d_session_fill(self._handle, C.byref(q), self._err, len(self._err)))
         got.update(filled_samples=int(stats[0]), fill_rounds=int(stats[1]), flat_rounds=int(stats[2]), largest_flat_distance=int(stats[3]))
         return got

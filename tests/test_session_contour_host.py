@@ -445,3 +445,59 @@ def test_wrapper_methods_and_argument_checks(monkeypatch):
         s.paint_contours([1.0], width=-1.0)
     with pytest.raises(ValueError, match=re.escape("opacity must lie in [0, 1]")):
         s.paint_contours([1.0], opacity=1.5)
+
+
+# ---- what contours() and streams(), paint_contours() and paint_streams() share in the wrapper: every text in full ------------
+def device_tensor(shape, dtype, contiguous=True):
+    """What the wrapper's checks see of a tensor on the session's device, without a device."""
+    import torch
+
+    members = {"__module__": "torch", "is_cuda": True, "ndim": len(shape), "shape": tuple(shape), "dtype": getattr(torch, dtype),
+               "is_contiguous": lambda self: contiguous, "data_ptr": lambda self: 256, "numel": lambda self: int(np.prod(shape))}
+    return type("Tensor", (), members)()
+
+
+class UntouchedLibrary:
+    """The session's library for a call that must be refused before it: an entry may be looked up, not called."""
+    def __getattr__(self, name):
+        def entry(*a):
+            raise AssertionError("the device was touched")
+        return entry
+
+
+def refused(text, call, *args, **kw):
+    with pytest.raises(ValueError, match="^" + re.escape(text) + "$"):
+        call(*args, **kw)
+
+
+def record_outputs_refusals(call, second):
+    """``call(out)``: contours() or streams() with their own arguments in place."""
+    seg_text = f"out=(segments, {second}): segments must be a contiguous float32 tensor (C, 4) on the session's device"
+    second_text = f"out=(segments, {second}): {second} must be a contiguous int32 tensor (C,) on the session's device, or None"
+    good = device_tensor((6, 4), "float32")
+    for seg in (np.zeros((6, 4), np.float32), [[0.0] * 4] * 6, device_tensor((6, 3), "float32"), device_tensor((6, 4), "float64"),
+                device_tensor((6, 4), "float32", contiguous=False), device_tensor((24,), "float32")):
+        refused(seg_text, call, (seg, None))
+        refused(seg_text, call, (seg, np.zeros(5)))  # (the segments' fault wins)
+    for word in (np.zeros(6, np.uint32), device_tensor((5,), "int32"), device_tensor((7,), "int32"), device_tensor((6,), "uint8"),
+                 device_tensor((6,), "int64"), device_tensor((6, 1), "int32"), device_tensor((6,), "int32", contiguous=False)):
+        refused(second_text, call, (good, word))
+
+
+def stroke_refusals(call):
+    """``call(**stroke)``: paint_contours() or paint_streams() with their own arguments in place."""
+    refused("rgba must be one colour of 3 or 4 numbers, got (2,)", call, rgba=(0.0, 1.0))
+    refused("rgba must be one colour of 3 or 4 numbers, got (5,)", call, rgba=(0.0, 1.0, 0.0, 1.0, 0.5))
+    refused("rgba must be one colour of 3 or 4 numbers, got (2,)", call, rgba=(0.0, 1.0), width=-1.0)  # (the colour's fault wins)
+    refused("width must be finite and >= 0 metres, got -1.0", call, width=-1.0)
+    refused("width must be finite and >= 0 metres, got nan", call, width=float("nan"))
+    refused("width must be finite and >= 0 metres, got -1.0", call, width=-1.0, opacity=1.5)  # (the width's fault wins)
+    refused("opacity must lie in [0, 1], got 1.5", call, opacity=1.5)
+
+
+def test_shared_refusals_of_the_record_outputs_and_the_stroke_in_the_contours_words(monkeypatch):
+    _no_device(monkeypatch)
+    s = _bare_session()
+    s._lib = UntouchedLibrary()
+    record_outputs_refusals(lambda out: s.contours([1.0], out=out), "level_index")
+    stroke_refusals(lambda **stroke: s.paint_contours([1.0], **stroke))

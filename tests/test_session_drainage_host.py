@@ -335,3 +335,36 @@ def test_wrapper_methods_and_argument_checks(monkeypatch):
     assert handle._streams["threshold"] == 50 and handle._streams["trunk_threshold"] == 500 and handle._revision == 1
     handle.disable_streams()
     assert handle._streams is None and handle._revision == 2
+
+
+def planes_refusals(call, names, dtypes, shape=(9, 9)):
+    """``call(out)``: drainage() or fill() on a bare session of ``shape``.  The planes by name: every text in full."""
+    from test_session_contour_host import device_tensor, refused
+
+    under = "out must be None, 'device' or a dict of tensors under " + ", ".join(repr(n) for n in names)
+    refused(under, call, "host")
+    refused(under, call, "")
+    refused(under, call, {"height": None})
+    refused(under, call, {names[0]: device_tensor(shape, dtypes[0]), "height": None})
+    for name, dtype in zip(names, dtypes):
+        text = f"out[{name!r}] must be a contiguous torch.{dtype} tensor ({shape[0]}, {shape[1]}) on the session's device"
+        other = "float64" if dtype != "float64" else "int32"
+        for plane in (np.zeros(shape), device_tensor((shape[0], shape[1] + 1), dtype), device_tensor((shape[0] * shape[1],), dtype),
+                      device_tensor(shape, other), device_tensor(shape, dtype, contiguous=False)):
+            refused(text, call, {name: plane})
+
+
+def test_shared_refusals_of_the_planes_the_record_outputs_and_the_stroke_in_the_drainage_words(monkeypatch):
+    from test_session_contour_host import UntouchedLibrary, record_outputs_refusals, stroke_refusals
+
+    _no_device(monkeypatch)
+    s = _bare_session()
+    s._lib = UntouchedLibrary()
+    assert [n for n, _, _ in s._DRAINAGE_PLANES] == ["direction", "accumulation", "basin"]
+    nothing = dict(direction=False, accumulation=False)  # (a plane that is wanted and not given is allocated on the way: on a device)
+    for call in (lambda out: s.drainage(out=out, **nothing), lambda out: s.filled.drainage(out=out, **nothing)):
+        planes_refusals(call, ("direction", "accumulation", "basin"), ("uint8", "int32", "int32"))
+    for streams in (s.streams, s.filled.streams):
+        record_outputs_refusals(lambda out: streams(5, out=out), "accumulation")
+    for paint in (s.paint_streams, s.filled.paint_streams):
+        stroke_refusals(lambda **stroke: paint(5, **stroke))

@@ -329,3 +329,13 @@ def test_wrapper_methods_and_argument_checks(monkeypatch):
     assert handle._streams["fill"] is False
     with pytest.raises(ViewerError):
         handle.enable_streams(0, fill=True)
+
+
+def test_shared_refusals_of_the_planes_in_the_fills_words(monkeypatch):
+    from test_session_drainage_host import planes_refusals
+
+    _no_device(monkeypatch)
+    s = _bare_session((7, 12))
+    # (filled=False: a plane that is wanted and not given is allocated on the way, on a device)
+    planes_refusals(lambda out: s.fill(filled=False, out=out), FILL_PLANES, ("float32", "float32", "int32"), (7, 12))
+    planes_refusals(lambda out: s.fill((1, 2, 3, 4), filled=False, out=out), FILL_PLANES, ("float32", "float32", "int32"), (3, 4))

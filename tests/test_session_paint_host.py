@@ -663,3 +663,16 @@ def test_the_facade_expands_strips_orders_layers_and_refuses_what_has_no_offline
         v.set_vector_canvas(0, 5)
     with pytest.raises(ViewerError, match="belongs to the interactive raster viewer"):
         v.add_label("x", (0, 0, 0))
+
+
+def test_the_stroke_of_paint_is_refused_in_the_words_the_derived_paints_share():
+    from test_session_contour_host import refused
+
+    s = _bare_session((33, 33))
+    xz, red = np.array([[0, 0], [10, 0]], f32), (1.0, 0.0, 0.0, 1.0)
+    refused("width must be finite and >= 0 metres, got -1.0", s.paint, xz, red, width=-1.0)
+    refused("width must be finite and >= 0 metres, got nan", s.paint, xz, red, width=float("nan"))
+    refused("width must be finite and >= 0 metres, got -1.0", s.paint, xz, red, width=-1.0, opacity=1.5)  # (the width's fault wins)
+    refused("opacity must lie in [0, 1], got 1.5", s.paint, xz, red, opacity=1.5)
+    refused("rgba must be one colour of 3 or 4 numbers or have shape (2, 3|4), got (2,)", s.paint, xz, (1.0, 0.0))  # (its colours stay its own)
+    refused("rgba must be one colour of 3 or 4 numbers or have shape (2, 3|4), got (5,)", s.paint, xz, (1.0, 0.0, 0.0, 1.0, 0.5), width=-1.0)
